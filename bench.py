@@ -10,8 +10,10 @@ collective on the data path.
 One JSON line on rank 0.  Extra keys: node_evals_per_s, roofline (dominant
 kernel: k_memo for FGD -- one persistent launch replays every replica with the
 (pod class, node) keys memoised -- else k_replay; priced against HBM with SURVEY
-§8(d)'s 32 B per node-evaluation + 56 B per pod), and cpu_baseline (the C oracle
--- a restatement of the Go path -- on the host cores).
+§8(d)'s 32 B per node-evaluation + 56 B per pod).  A plain run sets up, warms up,
+times --steps replays and prints the line; --full adds cpu_baseline (the C oracle
+-- a restatement of the Go path -- on the host cores), and --dump-outputs DIR
+writes the last timed step's results as DIR/*.npy (dump_outputs).
 
 Multi-GPU (torchrun, one rank per GPU): each rank replays its own seeds on its own
 GPU; the only collectives are the timing barrier and the job reduction (max time,
@@ -247,6 +249,57 @@ def latency_block(kern_us, steps, wgs):
     return out
 
 
+DUMP_BUDGET_BYTES = 60 << 20  # --dump-outputs: all the arrays of one run together stay under 64 MB
+DUMP_SAMPLE_SEED = 20240807
+RESULT_COLS = ("node", "gpu_mask", "score", "n_feasible", "status")
+REPORT_COLS = ("used_nodes", "used_gpus", "used_gpu_milli", "total_gpus", "arrived_gpu_milli", "used_cpu_milli",
+               "arrived_cpu_milli")
+
+
+def dump_rows(n_events, row_bytes, budget=DUMP_BUDGET_BYTES, seed=DUMP_SAMPLE_SEED):
+    """Per replica, the event indices --dump-outputs keeps: every event when all rows fit the budget, else a
+    fixed seeded sample of the rows of all replicas (sorted, without replacement; the same for every run
+    with the same arguments)."""
+    import numpy as np
+    total = int(sum(n_events))
+    keep = budget // row_bytes
+    if total <= keep:
+        return [np.arange(n, dtype=np.int64) for n in n_events]
+    pick = np.sort(np.random.default_rng(seed).choice(total, size=keep, replace=False))
+    ends = np.cumsum(n_events)
+    cuts = np.searchsorted(pick, ends, side="left")
+    return [pick[a:b] - (e - n) for a, b, e, n in zip([0] + list(cuts[:-1]), cuts, ends, n_events)]
+
+
+def dump_outputs(eng, directory, report=False, suffix=""):
+    """What the last run() computed, as a caller of the engine receives it: results<suffix>.npy, float64
+    [rows, 2 + 5] = (replica, event) + RESULT_COLS of Engine.results_array, and with the cluster report
+    reports<suffix>.npy, float64 [rows, 2 + 7 + 7] = (replica, event) + frag_bins + REPORT_COLS of
+    Engine.report_arrays.  Returns {file name: shape}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    n_events = [int(n) for n in eng.n_events]
+    row_bytes = 8 * (2 + len(RESULT_COLS)) + (8 * (2 + 7 + len(REPORT_COLS)) if report else 0)
+    rows = dump_rows(n_events, row_bytes)
+    res, rep = [], []
+    for r, idx in enumerate(rows):
+        if not len(idx):
+            continue
+        head = [np.full(len(idx), r, dtype=np.float64), idx.astype(np.float64)]
+        a = eng.results_array(r)
+        res.append(np.stack(head + [a[c][idx].astype(np.float64) for c in RESULT_COLS], axis=1))
+        if report:
+            d = eng.report_arrays(r)
+            rep.append(np.concatenate([np.stack(head, axis=1), d["frag_bins"][idx].astype(np.float64),
+                                       np.stack([d[c][idx].astype(np.float64) for c in REPORT_COLS], axis=1)], axis=1))
+    out = {"results%s.npy" % suffix: np.concatenate(res) if res else np.zeros((0, 2 + len(RESULT_COLS)))}
+    if report:
+        out["reports%s.npy" % suffix] = np.concatenate(rep) if rep else np.zeros((0, 2 + 7 + len(REPORT_COLS)))
+    for name, a in out.items():
+        np.save(os.path.join(directory, name), a)
+    return {name: list(a.shape) for name, a in out.items()}
+
+
 def seeds_for_rank(rank, replicas, base=42):
     """C2 seeds of one rank: rank k replays base + replicas*k .. base + replicas*(k+1) - 1."""
     return [base + replicas * rank + i for i in range(replicas)]
@@ -274,7 +327,15 @@ def main():
     ap.add_argument("--wgs", type=int, default=0, help="workgroups per replica (0 = auto)")
     ap.add_argument("--run-mode", type=int, default=0,
                     help="0 auto (FGD: k_memo), 1 k_step per pod, 2 k_replay only, 3 k_memo required")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baselines (cpu_baseline in the "
+                         "result line; the oracle on the host cores)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64): "
+                         "results.npy, one row per pod event (replica, event, node, gpu_mask, score, n_feasible, "
+                         "status), and with the cluster report reports.npy; a fixed seeded sample of the rows when "
+                         "all of them would exceed DUMP_BUDGET_BYTES")
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--policy", default="FGD", help="FGD (headline) | BestFit | DotProd | GpuPacking | GpuClustering | Random | PWR | "
                          "'PWR 500 FGD 500' ...")
@@ -294,13 +355,14 @@ def main():
                     help="Random policy: the hash contract (default) or the reference's draw structure on Go's "
                          "math/rand stream (k_random_go)")
     args = ap.parse_args()
+    cpu_base = args.full and not args.no_cpu_baseline  # a plain run measures the headline figure only
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # C4's CPU baseline first: its worker processes are spawned before anything here touches the GPU
     sweep_cpu = None
-    if args.config == "c4" and rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.config == "c4" and rank == 0 and world == 1 and cpu_base:
         sweep_cpu = cpu_baseline_sweep(workers=args.cpu_threads)
     # world 1 never imports torch: the process holds the one HIP runtime ksim binds (a profiler's, under
     # rocprofv3), and the engine's own run() synchronises and times the launch.  World > 1: torch.distributed
@@ -483,7 +545,7 @@ def main():
         line["report_ms_per_step"] = eng.last_report_ms()
     line["build_id"] = ksim.build_id()  # sha256 prefix of the library's sources (ksim.source_hash())
     line["hip_runtime"] = ksim.hip_runtimes()  # one HIP / HSA runtime per process
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "c2":
+    if rank == 0 and world == 1 and cpu_base and args.config == "c2":
         # like for like: the GPU line's seeds as single-threaded replicas on as many cores; beside it one
         # replica with `cpu_threads` workers per cycle (parallelize.Until) and one thread on a prefix
         one = cpu_baseline(trace, seeds[0], args.cpu_threads)
@@ -492,8 +554,12 @@ def main():
         line["cpu_baseline"]["single_thread"] = one["single_thread"]
     if sweep_cpu is not None:
         line["cpu_baseline"] = sweep_cpu
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and c5_rp is not None and args.policy == "FGD":
+    if rank == 0 and world == 1 and cpu_base and c5_rp is not None and args.policy == "FGD":
         line["cpu_baseline"] = cpu_baseline_c5(trace, c5_rp, args.cpu_threads)
+    if args.dump_outputs:
+        # the last timed step's results (and cluster reports), rank k's own files at world > 1
+        line["dumped_outputs"] = dump_outputs(eng, args.dump_outputs, args.config == "c4" or args.report,
+                                              "_rank%d" % rank if world > 1 else "")
     if rank == 0:
         print(json.dumps(line), flush=True)
     if os.environ.get("KSIM_MAPS_OUT"):  # the process's mappings, to symbolise an exit-path fault

@@ -11,6 +11,6 @@ tail -1 $O/pytest_gpu.log
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo "smoke rc=$?"; exit 1; }
 cat $O/smoke.log
 for c in c2 c4 c5; do
-  timeout -k 10 300 python -u bench.py --config $c > $O/bench_$c.json 2> $O/bench_$c.err || { echo "bench $c rc=$?"; tail -5 $O/bench_$c.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --config $c > $O/bench_$c.json 2> $O/bench_$c.err || { echo "bench $c rc=$?"; tail -5 $O/bench_$c.err; exit 1; }
   python3 -c "import json; d = json.load(open('$O/bench_$c.json')); print('$c', d['value'], d['unit'], round(d['ms_per_step'], 3), d.get('cpu_baseline', {}).get('value'))"
 done

@@ -35,9 +35,9 @@ def test_library_exports_every_declared_symbol():
     assert set(ksim.SIGNATURES) == names
 
 
-def test_struct_layouts_match_c():
+def test_struct_layouts_match_c(tmp_path):
     src = os.path.join(ROOT, "tests", "golden", "abi_sizes.c")
-    exe = "/tmp/ksim_abi_sizes"
+    exe = str(tmp_path / "ksim_abi_sizes")
     subprocess.run(["gcc", "-I" + os.path.join(ROOT, "include"), src, "-o", exe], check=True)
     got = list(map(int, subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()))
     want = [C.sizeof(t) for t in (ksim.Node, ksim.Pod, ksim.Typical, ksim.Result, ksim.Config, ksim.TraceNode,
