@@ -39,6 +39,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <vector>
 #include <chrono>
 #include <thread>
@@ -1771,6 +1772,8 @@ __global__ __launch_bounds__(64) void k_reserve(ReplicaDev* reps, const TypDev* 
 
 }  // namespace
 
+#include "ksim_host.hpp"
+
 // ---------------------------------------------------------------------------
 // Host engine object
 // ---------------------------------------------------------------------------
@@ -1783,13 +1786,10 @@ struct ksim_engine {
   int cus = 256;
   bool coop = true;  // K > 1 persistent grids through hipLaunchCooperativeKernel (KSIM_COOP=0: plain launch)
   unsigned long long* d_gran = nullptr;
-  int2* d_hist = nullptr;
-  size_t hist_cap = 0;
+  DevBuf<int2> d_hist;
   int* d_fail = nullptr;
   int* d_replist = nullptr;              // replicas ordered by policy (k_replay groups)
-  int last_groups = 0;
-  unsigned long long* d_prof = nullptr;  // KSIM_PROFILE=1: k_replay phase timers
-  size_t prof_cap = 0;
+  DevBuf<unsigned long long> d_prof;  // KSIM_PROFILE=1: k_replay phase timers
   int last_K = 0;
   hipStream_t stream = nullptr;
   NodeRec* d_nodes = nullptr;
@@ -1819,26 +1819,22 @@ struct ksim_engine {
   std::vector<std::vector<TypDev>> h_tp;  // each replica's typical table as uploaded (k_hmemo's per-model tables)
   std::vector<std::vector<int>> h_cls_n;
   std::vector<std::vector<int>> h_ev_cls;  // class of each event, -1 delete
-  PodDev* d_m_pod = nullptr;
-  int* d_m_owner = nullptr;
-  int* d_m_wgcls = nullptr;
-  int* d_m_wgref = nullptr;
-  unsigned long long* d_m_wggrp = nullptr;
-  unsigned* d_win = nullptr;
-  int* d_m_evo = nullptr;
-  int* d_m_evcls = nullptr;     // decider mode: class of each event
-  unsigned* d_topg = nullptr;   // decider mode: top granules
-  unsigned* d_m_hkeys = nullptr;  // k_memo with the keys in HBM (MemoPlan::hkeys)
-  int* d_m_wgmap = nullptr;       // k_memo: each block's launch position << 8 | workgroup (MemoArgs::wg_map)
-  unsigned long long* d_done = nullptr;  // [2 + R] the overlapped report's queue (ksim_scan1.hpp Scan1Args::done)
-  __int128* d_ragg = nullptr;     // [R][kScanPartsMax][2][kFields] the multi-workgroup report scan's part sums
-  size_t ragg_cap = 0;
-  int done_cap = 0;
+  DevBuf<PodDev> d_m_pod;
+  DevBuf<int> d_m_owner;
+  DevBuf<int> d_m_wgcls;
+  DevBuf<int> d_m_wgref;
+  DevBuf<unsigned long long> d_m_wggrp;
+  DevBuf<unsigned> d_win;
+  DevBuf<int> d_m_evo;
+  DevBuf<int> d_m_evcls;     // decider mode: class of each event
+  DevBuf<unsigned> d_topg;   // decider mode: top granules
+  DevBuf<unsigned> d_m_hkeys;  // k_memo with the keys in HBM (MemoPlan::hkeys)
+  DevBuf<int> d_m_wgmap;       // k_memo: each block's launch position << 8 | workgroup (MemoArgs::wg_map)
+  DevBuf<unsigned long long> d_done;  // [2 + R] the overlapped report's queue (ksim_scan1.hpp Scan1Args::done)
+  DevBuf<__int128> d_ragg;     // [R][kScanPartsMax][2][kFields] the multi-workgroup report scan's part sums
   unsigned done_epoch = 0;
   hipEvent_t ev_ovl = nullptr;    // the queue's tickets zeroed (the report's stream waits on it)
-  size_t m_cap2[4] = {0, 0, 0, 0};
   double* d_th = nullptr;       // FGD score steps (build_score_thresholds), null if unusable
-  size_t m_cap[7] = {0, 0, 0, 0, 0, 0, 0};
   struct MemoPlan* mplan = nullptr;  // the FGD replicas' k_memo plan, uploaded before the timed run
   bool mplan_dirty = true;           // events or policies changed since the plan was made
   bool mplan_ok = false;
@@ -1852,25 +1848,24 @@ struct ksim_engine {
   // k_hmemo (memoised FGD replay, keys in HBM): the plan and its device tables
   struct HPlan* hplan = nullptr;
   bool hplan_ok = false;
-  int* d_h_cg = nullptr;
-  PodDev* d_h_cls = nullptr;
-  uint16_t* d_h_cgrp = nullptr;
-  PodDev* d_h_gpod = nullptr;
-  int* d_h_mtoff = nullptr;      // k_hmemo's per-model tables (typed replicas)
-  uint8_t* d_h_mtab = nullptr;
-  double* d_h_na = nullptr;      // their NA bins per (model, total), k_hinit_na
-  int* d_h_evc = nullptr;
-  NodeRec* d_h_st = nullptr;
-  int* d_h_ns = nullptr;
-  int* d_h_nstate = nullptr;
-  unsigned* d_h_gsc = nullptr;
-  unsigned* d_h_keys = nullptr;
-  unsigned* d_h_l1 = nullptr;
-  unsigned* d_h_l2 = nullptr;  // k_hmemo: initial second maxima (HPlan::l2)
-  int* d_h_cnt = nullptr;
-  unsigned long long* d_h_prof = nullptr;
-  uint8_t* d_h_hist = nullptr;  // wide k_hmemo with deletes: per-workgroup bind history
-  size_t h_cap[18] = {};
+  DevBuf<int> d_h_cg;
+  DevBuf<PodDev> d_h_cls;
+  DevBuf<uint16_t> d_h_cgrp;
+  DevBuf<PodDev> d_h_gpod;
+  DevBuf<int> d_h_mtoff;      // k_hmemo's per-model tables (typed replicas)
+  DevBuf<uint8_t> d_h_mtab;
+  DevBuf<double> d_h_na;      // their NA bins per (model, total), k_hinit_na
+  DevBuf<int> d_h_evc;
+  DevBuf<NodeRec> d_h_st;
+  DevBuf<int> d_h_ns;
+  DevBuf<int> d_h_nstate;
+  DevBuf<unsigned> d_h_gsc;
+  DevBuf<unsigned> d_h_keys;
+  DevBuf<unsigned> d_h_l1;
+  DevBuf<unsigned> d_h_l2;  // k_hmemo: initial second maxima (HPlan::l2)
+  DevBuf<int> d_h_cnt;
+  DevBuf<unsigned long long> d_h_prof;
+  DevBuf<uint8_t> d_h_hist;  // wide k_hmemo with deletes: per-workgroup bind history
   int last_hmemo = 0;
   int last_rgo = 0;  // replicas the last run replayed on k_random_go
   int last_scan1 = 0;  // replicas the last run replayed on k_scan1
@@ -1891,7 +1886,7 @@ struct ksim_engine {
   std::vector<char> pw_set;  // set_power_model called
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_mid = nullptr;
   // side streams for concurrent single-workgroup k_replay groups (created on first use)
-  static constexpr int kSide = 6;
+  static constexpr int kSide = kSideStreams;
   hipStream_t side[kSide] = {};
   int* h_started = nullptr;   // residency gate: host-mapped flags, one per FGD workgroup (hipHostMalloc)
   int* d_started = nullptr;   // its device address
@@ -1944,30 +1939,9 @@ struct ksim_engine {
   // the Random draw structure on Go's math/rand stream (ksim_engine_set_go_stream): per replica the
   // source state {vec[607], tap, feed}, empty = the hash contract
   std::vector<std::vector<unsigned long long>> go_state;
-  unsigned long long* d_go = nullptr;
-  size_t go_cap = 0;
+  DevBuf<unsigned long long> d_go;
   int64_t last_steps = 0;
 };
-
-// Environment knobs.  Besides the five plain ones (KSIM_PROFILE, KSIM_COOP, KSIM_CUS,
-// KSIM_SIDE_STREAMS, KSIM_GROUP_TIMES), two comma-separated key=value lists: KSIM_VARIANT selects the measured
-// alternative forms of the kernels and plans (A/B runs; the defaults are what the bench and the tests measure),
-// KSIM_TEST the test-only settings (wrap points, stress delays, forced misses).
-static long knob(const char* var, const char* key, long dflt) {
-  const char* v = std::getenv(var);
-  if (!v) return dflt;
-  const size_t kl = std::strlen(key);
-  for (const char* p = v; *p;) {
-    const char* q = std::strchr(p, ',');
-    const size_t len = q ? (size_t)(q - p) : std::strlen(p);
-    if (len > kl && std::strncmp(p, key, kl) == 0 && p[kl] == '=') return std::strtol(p + kl + 1, nullptr, 0);
-    if (!q) break;
-    p = q + 1;
-  }
-  return dflt;
-}
-static long variant(const char* key, long dflt) { return knob("KSIM_VARIANT", key, dflt); }
-static long test_knob(const char* key, long dflt) { return knob("KSIM_TEST", key, dflt); }
 
 static int check_gfx950(int dev) {
   int n = 0;
@@ -1990,7 +1964,7 @@ static int upload_reps(ksim_engine* e) {
 // CUs the engine may use: the occupancy query times the CU count.  A persistent grid whose workgroups
 // exchange granules (K > 1) must not exceed it.
 static int resident_cap(const ksim_engine* e, const void* f, size_t lds);
-static int run_hmemo_peer(ksim_engine* e, int max_ev);
+static int run_hmemo_peer(ksim_engine* e, const RunEnv& env, int max_ev);
 
 // A persistent launch: K > 1 workgroups per replica poll each other's granules every step, so the
 // whole grid must be resident -- a cooperative launch, which the runtime refuses up front
@@ -2220,16 +2194,6 @@ static bool memo_plan(const ksim_engine* e, const std::vector<int>& reps, MemoPl
   return true;
 }
 
-template <typename T>
-static int ensure_buf(T*& p, size_t& cap, size_t n) {
-  if (n <= cap && p) return KSIM_OK;
-  if (p) KSIM_HIP(hipFree(p));
-  p = nullptr;
-  KSIM_HIP(hipMalloc(&p, sizeof(T) * std::max(n, (size_t)1)));
-  cap = n;
-  return KSIM_OK;
-}
-
 // The FGD score steps, built once per process on the host (nullptr if the check fails: k_memo
 // then evaluates the sigmoid expression itself).
 static const double* score_table() {
@@ -2414,14 +2378,6 @@ static bool hmemo_plan(const ksim_engine* e, const std::vector<int>& reps, int s
   return true;
 }
 
-template <typename T>
-static int upload_vec(T*& p, size_t& cap, const std::vector<T>& v, hipStream_t st) {
-  int rc = ensure_buf(p, cap, v.size());
-  if (rc) return rc;
-  KSIM_HIP(hipMemcpyAsync(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, st));
-  return KSIM_OK;
-}
-
 static int prepare_hmemo(ksim_engine* e, const std::vector<int>& reps, int max_ev, int forceK = 0, int forceS = 0) {
   e->hplan_ok = false;
   if (!e->hplan) e->hplan = new HPlan();
@@ -2432,23 +2388,23 @@ static int prepare_hmemo(ksim_engine* e, const std::vector<int>& reps, int max_e
   e->hplan_reps = reps;
   hipStream_t st = e->stream;
   int rc;
-  if ((rc = upload_vec(e->d_h_cg, e->h_cap[0], pl.cg, st))) return rc;
-  if ((rc = upload_vec(e->d_h_cls, e->h_cap[1], pl.cls, st))) return rc;
-  if ((rc = upload_vec(e->d_h_cgrp, e->h_cap[2], pl.cgrp, st))) return rc;
-  if ((rc = upload_vec(e->d_h_gpod, e->h_cap[3], pl.gpod, st))) return rc;
-  if ((rc = upload_vec(e->d_h_evc, e->h_cap[4], pl.evc, st))) return rc;
-  if ((rc = upload_vec(e->d_h_st, e->h_cap[5], pl.st, st))) return rc;
-  if ((rc = upload_vec(e->d_h_ns, e->h_cap[6], pl.ns, st))) return rc;
-  if ((rc = upload_vec(e->d_h_nstate, e->h_cap[7], pl.nstate, st))) return rc;
-  if ((rc = ensure_buf(e->d_h_gsc, e->h_cap[8], (size_t)Rg * pl.Gmax * pl.Smax))) return rc;
-  if ((rc = ensure_buf(e->d_h_keys, e->h_cap[9], (size_t)Rg * pl.Cmax * pl.Npad))) return rc;
-  if ((rc = ensure_buf(e->d_h_l1, e->h_cap[10], (size_t)Rg * pl.Cmax * pl.nb))) return rc;
-  if (pl.l2 && (rc = ensure_buf(e->d_h_l2, e->h_cap[14], (size_t)Rg * pl.Cmax * pl.nb))) return rc;
-  if ((rc = ensure_buf(e->d_h_cnt, e->h_cap[11], (size_t)Rg * pl.Cmax))) return rc;
+  if ((rc = e->d_h_cg.upload(pl.cg, st))) return rc;
+  if ((rc = e->d_h_cls.upload(pl.cls, st))) return rc;
+  if ((rc = e->d_h_cgrp.upload(pl.cgrp, st))) return rc;
+  if ((rc = e->d_h_gpod.upload(pl.gpod, st))) return rc;
+  if ((rc = e->d_h_evc.upload(pl.evc, st))) return rc;
+  if ((rc = e->d_h_st.upload(pl.st, st))) return rc;
+  if ((rc = e->d_h_ns.upload(pl.ns, st))) return rc;
+  if ((rc = e->d_h_nstate.upload(pl.nstate, st))) return rc;
+  if ((rc = e->d_h_gsc.ensure((size_t)Rg * pl.Gmax * pl.Smax))) return rc;
+  if ((rc = e->d_h_keys.ensure((size_t)Rg * pl.Cmax * pl.Npad))) return rc;
+  if ((rc = e->d_h_l1.ensure((size_t)Rg * pl.Cmax * pl.nb))) return rc;
+  if (pl.l2 && (rc = e->d_h_l2.ensure((size_t)Rg * pl.Cmax * pl.nb))) return rc;
+  if ((rc = e->d_h_cnt.ensure((size_t)Rg * pl.Cmax))) return rc;
   if (pl.Mtab > 0) {
-    if ((rc = upload_vec(e->d_h_mtoff, e->h_cap[15], pl.mtoff, st))) return rc;
-    if ((rc = upload_vec(e->d_h_mtab, e->h_cap[16], pl.mtab, st))) return rc;
-    if ((rc = ensure_buf(e->d_h_na, e->h_cap[17], (size_t)Rg * pl.Mslots * ksim_hmemo::kNaStride))) return rc;
+    if ((rc = e->d_h_mtoff.upload(pl.mtoff, st))) return rc;
+    if ((rc = e->d_h_mtab.upload(pl.mtab, st))) return rc;
+    if ((rc = e->d_h_na.ensure((size_t)Rg * pl.Mslots * ksim_hmemo::kNaStride))) return rc;
   }
   if (!e->d_th) {
     KSIM_HIP(hipMalloc(&e->d_th, sizeof(double) * 102));
@@ -2519,16 +2475,16 @@ static int upload_memo(ksim_engine* e, const std::vector<int>& reps, int max_ev)
   MemoPlan& pl = *e->mplan;
   const int Rg = (int)reps.size();
   int rc;
-  if ((rc = ensure_buf(e->d_m_pod, e->m_cap[0], pl.pod.size()))) return rc;
-  if ((rc = ensure_buf(e->d_m_owner, e->m_cap[1], pl.owner.size()))) return rc;
-  if ((rc = ensure_buf(e->d_m_wgcls, e->m_cap[2], pl.wgcls.size()))) return rc;
-  if ((rc = ensure_buf(e->d_m_wgref, e->m_cap[3], pl.wgref.size()))) return rc;
-  if ((rc = ensure_buf(e->d_m_wggrp, e->m_cap[4], pl.wggrp.size()))) return rc;
+  if ((rc = e->d_m_pod.ensure(pl.pod.size()))) return rc;
+  if ((rc = e->d_m_owner.ensure(pl.owner.size()))) return rc;
+  if ((rc = e->d_m_wgcls.ensure(pl.wgcls.size()))) return rc;
+  if ((rc = e->d_m_wgref.ensure(pl.wgref.size()))) return rc;
+  if ((rc = e->d_m_wggrp.ensure(pl.wggrp.size()))) return rc;
   const int stride = std::max(max_ev, 1);
-  if ((rc = ensure_buf(e->d_win, e->m_cap[5], (size_t)Rg * stride))) return rc;
-  if ((rc = ensure_buf(e->d_m_evo, e->m_cap[6], (size_t)Rg * stride))) return rc;
-  if ((rc = ensure_buf(e->d_m_evcls, e->m_cap2[0], (size_t)Rg * stride))) return rc;
-  if ((rc = ensure_buf(e->d_topg, e->m_cap2[1], (size_t)Rg * stride * ksim_memo::kTopWords))) return rc;
+  if ((rc = e->d_win.ensure((size_t)Rg * stride))) return rc;
+  if ((rc = e->d_m_evo.ensure((size_t)Rg * stride))) return rc;
+  if ((rc = e->d_m_evcls.ensure((size_t)Rg * stride))) return rc;
+  if ((rc = e->d_topg.ensure((size_t)Rg * stride * ksim_memo::kTopWords))) return rc;
   std::vector<int> evcls((size_t)Rg * stride, -1);
   for (int gi = 0; gi < Rg; ++gi) {
     const std::vector<int>& ec = e->h_ev_cls[reps[gi]];
@@ -2547,13 +2503,13 @@ static int upload_memo(ksim_engine* e, const std::vector<int>& reps, int max_ev)
     }
   }
   hipStream_t st = e->stream;
-  KSIM_HIP(hipMemcpyAsync(e->d_m_evo, evo.data(), sizeof(int) * evo.size(), hipMemcpyHostToDevice, st));
-  KSIM_HIP(hipMemcpyAsync(e->d_m_evcls, evcls.data(), sizeof(int) * evcls.size(), hipMemcpyHostToDevice, st));
-  KSIM_HIP(hipMemcpyAsync(e->d_m_pod, pl.pod.data(), sizeof(PodDev) * pl.pod.size(), hipMemcpyHostToDevice, st));
-  KSIM_HIP(hipMemcpyAsync(e->d_m_owner, pl.owner.data(), sizeof(int) * pl.owner.size(), hipMemcpyHostToDevice, st));
-  KSIM_HIP(hipMemcpyAsync(e->d_m_wgcls, pl.wgcls.data(), sizeof(int) * pl.wgcls.size(), hipMemcpyHostToDevice, st));
-  KSIM_HIP(hipMemcpyAsync(e->d_m_wgref, pl.wgref.data(), sizeof(int) * pl.wgref.size(), hipMemcpyHostToDevice, st));
-  KSIM_HIP(hipMemcpyAsync(e->d_m_wggrp, pl.wggrp.data(), sizeof(unsigned long long) * pl.wggrp.size(),
+  KSIM_HIP(hipMemcpyAsync(e->d_m_evo.p, evo.data(), sizeof(int) * evo.size(), hipMemcpyHostToDevice, st));
+  KSIM_HIP(hipMemcpyAsync(e->d_m_evcls.p, evcls.data(), sizeof(int) * evcls.size(), hipMemcpyHostToDevice, st));
+  KSIM_HIP(hipMemcpyAsync(e->d_m_pod.p, pl.pod.data(), sizeof(PodDev) * pl.pod.size(), hipMemcpyHostToDevice, st));
+  KSIM_HIP(hipMemcpyAsync(e->d_m_owner.p, pl.owner.data(), sizeof(int) * pl.owner.size(), hipMemcpyHostToDevice, st));
+  KSIM_HIP(hipMemcpyAsync(e->d_m_wgcls.p, pl.wgcls.data(), sizeof(int) * pl.wgcls.size(), hipMemcpyHostToDevice, st));
+  KSIM_HIP(hipMemcpyAsync(e->d_m_wgref.p, pl.wgref.data(), sizeof(int) * pl.wgref.size(), hipMemcpyHostToDevice, st));
+  KSIM_HIP(hipMemcpyAsync(e->d_m_wggrp.p, pl.wggrp.data(), sizeof(unsigned long long) * pl.wggrp.size(),
                           hipMemcpyHostToDevice, st));
   if (!e->d_th && score_table()) {
     KSIM_HIP(hipMalloc(&e->d_th, sizeof(double) * 102));
@@ -2562,62 +2518,57 @@ static int upload_memo(ksim_engine* e, const std::vector<int>& reps, int max_ev)
   std::vector<int> wgmap((size_t)pl.nwg);
   for (int gi = 0; gi < Rg; ++gi)
     for (int w = 0; w < pl.Kr[gi]; ++w) wgmap[(size_t)pl.wgoff[gi] + w] = (gi << 8) | w;
-  if ((rc = ensure_buf(e->d_m_wgmap, e->m_cap2[3], wgmap.size()))) return rc;
-  KSIM_HIP(hipMemcpyAsync(e->d_m_wgmap, wgmap.data(), sizeof(int) * wgmap.size(), hipMemcpyHostToDevice, st));
+  if ((rc = e->d_m_wgmap.ensure(wgmap.size()))) return rc;
+  KSIM_HIP(hipMemcpyAsync(e->d_m_wgmap.p, wgmap.data(), sizeof(int) * wgmap.size(), hipMemcpyHostToDevice, st));
   KSIM_HIP(hipStreamSynchronize(st));  // the host vectors are pageable and short-lived
-  if (pl.hkeys && (rc = ensure_buf(e->d_m_hkeys, e->m_cap2[2], (size_t)pl.nwg * pl.Cw * e->N))) return rc;
+  if (pl.hkeys && (rc = e->d_m_hkeys.ensure((size_t)pl.nwg * pl.Cw * e->N))) return rc;
   e->mplan_reps = reps;
   e->mplan_ok = true;
   return KSIM_OK;
 }
 
-// KSIM_TEST=hdelay=<mask>: the memoised kernels' hand-over stress delays (ksim_memo.hpp hdelay; the bits are
-// per kernel); a nonzero mask selects the general (non-lean) instantiation, which alone carries them.
-static int hdelay_mask() { return (int)(test_knob("hdelay", 0) & 0xff); }
-
 // st: the stream (a concurrent run's side stream, else the engine's); started / gate_epoch: the residency gate's
 // flags (a concurrent run launches the next group once every workgroup of this one has started: a plain launch
 // then, since the device is otherwise idle until the gate opens)
-static int launch_memo(ksim_engine* e, const MemoPlan& pl, int Rg, int first, int max_ev, hipStream_t st,
+static int launch_memo(ksim_engine* e, const RunEnv& env, const MemoPlan& pl, int Rg, int first, int max_ev, hipStream_t st,
                        int* started = nullptr, int gate_epoch = 0) {
   int rc;
   const int stride = std::max(max_ev, 1);
-  KSIM_HIP(hipMemsetAsync(e->d_win, 0, sizeof(unsigned) * (size_t)Rg * stride, st));
+  KSIM_HIP(hipMemsetAsync(e->d_win.p, 0, sizeof(unsigned) * (size_t)Rg * stride, st));
   if (pl.decider)
-    KSIM_HIP(hipMemsetAsync(e->d_topg, 0, sizeof(unsigned) * (size_t)Rg * stride * ksim_memo::kTopWords, st));
+    KSIM_HIP(hipMemsetAsync(e->d_topg.p, 0, sizeof(unsigned) * (size_t)Rg * stride * ksim_memo::kTopWords, st));
   ksim_memo::MemoArgs ma;
   ma.reps = e->d_reps;
   ma.rep_list = e->d_replist + first;
-  ma.wg_map = e->d_m_wgmap;
+  ma.wg_map = e->d_m_wgmap.p;
   ma.N = e->N;
   ma.K = pl.K;
   ma.Cw = pl.Cw;
   ma.nfw = pl.nfw;
   ma.Cmax = pl.Cmax;
-  ma.cls_pod = e->d_m_pod;
-  ma.cls_owner = e->d_m_owner;
-  ma.wg_cls = e->d_m_wgcls;
-  ma.wg_ref = e->d_m_wgref;
-  ma.wg_grp = e->d_m_wggrp;
-  ma.ev_owner = e->d_m_evo;
+  ma.cls_pod = e->d_m_pod.p;
+  ma.cls_owner = e->d_m_owner.p;
+  ma.wg_cls = e->d_m_wgcls.p;
+  ma.wg_ref = e->d_m_wgref.p;
+  ma.wg_grp = e->d_m_wggrp.p;
+  ma.ev_owner = e->d_m_evo.p;
   ma.th = e->d_th;
-  ma.win = e->d_win;
+  ma.win = e->d_win.p;
   ma.win_stride = stride;
   ma.fail = e->d_fail;
   ma.prof = nullptr;
   ma.trace = nullptr;
   ma.trace_steps = 0;
   ma.decider = pl.decider ? 1 : 0;
-  ma.ev_cls = e->d_m_evcls;
-  ma.topg = e->d_topg;
-  ma.hkeys = pl.hkeys ? e->d_m_hkeys : nullptr;
+  ma.ev_cls = e->d_m_evcls.p;
+  ma.topg = e->d_topg.p;
+  ma.hkeys = pl.hkeys ? e->d_m_hkeys.p : nullptr;
   ma.started = started;
   ma.gate_epoch = gate_epoch;
-  ma.skip = variant("skip", 1) != 0;
-  ma.delay = hdelay_mask();
-  const char* pe = std::getenv("KSIM_PROFILE");
-  const bool profile = pe && pe[0] == '1';
-  const bool tracing = pe && pe[0] == '2';
+  ma.skip = env.skip;
+  ma.delay = env.hdelay;
+  const bool profile = env.timers();
+  const bool tracing = env.profile == 2;
   unsigned long long* d_trace = nullptr;
   const int TS = std::min(max_ev, 4000);
   constexpr int kT = ksim_memo::kTrace;
@@ -2628,9 +2579,9 @@ static int launch_memo(ksim_engine* e, const MemoPlan& pl, int Rg, int first, in
     ma.trace_steps = TS;
   }
   if (profile) {
-    if ((rc = ensure_buf(e->d_prof, e->prof_cap, (size_t)pl.nwg * ksim_memo::kProfPhases))) return rc;
-    KSIM_HIP(hipMemsetAsync(e->d_prof, 0, sizeof(unsigned long long) * (size_t)pl.nwg * ksim_memo::kProfPhases, st));
-    ma.prof = e->d_prof;
+    if ((rc = e->d_prof.ensure((size_t)pl.nwg * ksim_memo::kProfPhases))) return rc;
+    KSIM_HIP(hipMemsetAsync(e->d_prof.p, 0, sizeof(unsigned long long) * (size_t)pl.nwg * ksim_memo::kProfPhases, st));
+    ma.prof = e->d_prof.p;
   }
   // the general instantiation for the profile / trace / deletes / no score table, else the lean one (with the
   // report's stores when the report is on)
@@ -2660,7 +2611,7 @@ static int launch_memo(ksim_engine* e, const MemoPlan& pl, int Rg, int first, in
     KSIM_HIP(hipMemcpy(h.data(), d_trace, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
     KSIM_HIP(hipFree(d_trace));
     std::vector<int> evo((size_t)TS);
-    KSIM_HIP(hipMemcpy(evo.data(), e->d_m_evo, sizeof(int) * TS, hipMemcpyDeviceToHost));
+    KSIM_HIP(hipMemcpy(evo.data(), e->d_m_evo.p, sizeof(int) * TS, hipMemcpyDeviceToHost));
     auto at = [&](int w, int s, int k) { return (double)h[((size_t)w * TS + s) * kT + k]; };
     double crit = 0, hand = 0, hmax = 0, period = 0, lag = 0, f0 = 0, spin = 0;
     int nc = 0, nh = 0, nf = 0;
@@ -2694,7 +2645,7 @@ static int launch_memo(ksim_engine* e, const MemoPlan& pl, int Rg, int first, in
     KSIM_HIP(hipStreamSynchronize(st));
     const int nb = pl.nwg, P = ksim_memo::kProfPhases;
     std::vector<unsigned long long> h((size_t)nb * P);
-    KSIM_HIP(hipMemcpy(h.data(), e->d_prof, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
+    KSIM_HIP(hipMemcpy(h.data(), e->d_prof.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
     static const char* names[] = {"init", "A:crit-F+list", "syncA", "B:publish", "B:eval", "syncB", "C:keys", "top2",
                                   "poll+bind", "end-sync"};
     std::fprintf(stderr, "ksim memo profile: %d workgroups (K=%d Cw=%d nfw=%d), %d steps; us/step mean [max]:", nb, pl.K,
@@ -2752,28 +2703,28 @@ static int hmemo_init_keys(ksim_engine* e, int Rg, int first, hipStream_t st, in
   ia.Cmax = pl.Cmax;
   ia.Gmax = pl.Gmax;
   ia.Smax = pl.Smax;
-  ia.cg = e->d_h_cg;
-  ia.cls = e->d_h_cls;
-  ia.cgrp = e->d_h_cgrp;
-  ia.gpod = e->d_h_gpod;
-  ia.st = e->d_h_st;
-  ia.ns = e->d_h_ns;
-  ia.nstate = e->d_h_nstate;
-  ia.gsc = e->d_h_gsc;
-  ia.keys = e->d_h_keys;
-  ia.l1 = e->d_h_l1;
-  ia.l2 = pl.l2 ? e->d_h_l2 : nullptr;
-  ia.cnt = e->d_h_cnt;
+  ia.cg = e->d_h_cg.p;
+  ia.cls = e->d_h_cls.p;
+  ia.cgrp = e->d_h_cgrp.p;
+  ia.gpod = e->d_h_gpod.p;
+  ia.st = e->d_h_st.p;
+  ia.ns = e->d_h_ns.p;
+  ia.nstate = e->d_h_nstate.p;
+  ia.gsc = e->d_h_gsc.p;
+  ia.keys = e->d_h_keys.p;
+  ia.l1 = e->d_h_l1.p;
+  ia.l2 = pl.l2 ? e->d_h_l2.p : nullptr;
+  ia.cnt = e->d_h_cnt.p;
   ia.th = e->d_th;
-  ia.mtoff = pl.Mtab > 0 ? e->d_h_mtoff : nullptr;
-  ia.na = pl.Mtab > 0 ? e->d_h_na : nullptr;
+  ia.mtoff = pl.Mtab > 0 ? e->d_h_mtoff.p : nullptr;
+  ia.na = pl.Mtab > 0 ? e->d_h_na.p : nullptr;
   ia.Mslots = pl.Mslots;
   if (pl.Mtab > 0) {
     hipLaunchKernelGGL(k_hinit_na, dim3((unsigned)((kNaStride + 255) / 256), (unsigned)pl.Mslots, (unsigned)Rg), dim3(256), 0,
                        st, ia, (const TypDev*)e->d_tp);
     KSIM_HIP(hipGetLastError());
   }
-  KSIM_HIP(hipMemsetAsync(e->d_h_cnt, 0, sizeof(int) * (size_t)Rg * pl.Cmax, st));
+  KSIM_HIP(hipMemsetAsync(e->d_h_cnt.p, 0, sizeof(int) * (size_t)Rg * pl.Cmax, st));
   hipLaunchKernelGGL(k_hinit_gk, dim3((unsigned)((pl.Smax + 255) / 256), (unsigned)pl.Gmax, (unsigned)Rg), dim3(256), 0,
                      st, ia, (const TypDev*)e->d_tp);
   KSIM_HIP(hipGetLastError());
@@ -2783,10 +2734,10 @@ static int hmemo_init_keys(ksim_engine* e, int Rg, int first, hipStream_t st, in
   return KSIM_OK;
 }
 
-static bool dead_skip(const ksim_engine* e, const std::vector<int>& reps);
+static bool dead_skip(const ksim_engine* e, const RunEnv& env, const std::vector<int>& reps);
 
 // k_hmemo's arguments for the planned launch (one group of Rg replicas from d_replist + first).
-static ksim_hmemo::HMemoArgs hmemo_args(ksim_engine* e, int first, int stride) {
+static ksim_hmemo::HMemoArgs hmemo_args(ksim_engine* e, const RunEnv& env, int first, int stride) {
   using namespace ksim_hmemo;
   const HPlan& pl = *e->hplan;
   HMemoArgs ma;
@@ -2795,24 +2746,24 @@ static ksim_hmemo::HMemoArgs hmemo_args(ksim_engine* e, int first, int stride) {
   ma.rep_list = e->d_replist + first;
   ma.Mtab = pl.Mtab;
   ma.Mslots = pl.Mslots;
-  ma.mtoff = pl.Mtab > 0 ? e->d_h_mtoff : nullptr;
-  ma.mtab = pl.Mtab > 0 ? e->d_h_mtab : nullptr;
-  ma.na = pl.Mtab > 0 ? e->d_h_na : nullptr;
+  ma.mtoff = pl.Mtab > 0 ? e->d_h_mtoff.p : nullptr;
+  ma.mtab = pl.Mtab > 0 ? e->d_h_mtab.p : nullptr;
+  ma.na = pl.Mtab > 0 ? e->d_h_na.p : nullptr;
   ma.N = e->N;
   ma.Npad = pl.Npad;
   ma.nb = pl.nb;
   ma.Cmax = pl.Cmax;
   ma.Gmax = pl.Gmax;
-  ma.cg = e->d_h_cg;
-  ma.cls = e->d_h_cls;
-  ma.cgrp = e->d_h_cgrp;
-  ma.gpod = e->d_h_gpod;
-  ma.evc = e->d_h_evc;
+  ma.cg = e->d_h_cg.p;
+  ma.cls = e->d_h_cls.p;
+  ma.cgrp = e->d_h_cgrp.p;
+  ma.gpod = e->d_h_gpod.p;
+  ma.evc = e->d_h_evc.p;
   ma.stride = stride;
-  ma.keys = e->d_h_keys;
-  ma.l1 = e->d_h_l1;
-  ma.l2 = pl.l2 ? e->d_h_l2 : nullptr;
-  ma.cnt0 = e->d_h_cnt;
+  ma.keys = e->d_h_keys.p;
+  ma.l1 = e->d_h_l1.p;
+  ma.l2 = pl.l2 ? e->d_h_l2.p : nullptr;
+  ma.cnt0 = e->d_h_cnt.p;
   ma.th = e->d_th;
   ma.prof = nullptr;
   ma.K = pl.K;
@@ -2830,13 +2781,13 @@ static ksim_hmemo::HMemoArgs hmemo_args(ksim_engine* e, int first, int stride) {
   {
     std::vector<int> all(e->R);
     std::iota(all.begin(), all.end(), 0);
-    ma.skip = dead_skip(e, all) ? 1 : 0;
+    ma.skip = dead_skip(e, env, all) ? 1 : 0;
   }
   {  // KSIM_VARIANT hpf (one workgroup per replica): 1 = wave 0 lists the next refresh (the default since r04: C4 190.7 ->
      // 178-185 ms, C2 run_mode 5 50.3 -> 47.7 ms, profiles/r04/memo/ab_runs.txt), 2 = touches its flagged rows, 0 = off
     ma.pf = (int)variant("hpf", 1) & 7;  // (4: the wide form lists on wave 0 too)
   }
-  ma.delay = hdelay_mask();
+  ma.delay = env.hdelay;
   {  // KSIM_VARIANT hprune (A/B): the F list's group pruning for replicas with more than this many typical pods
     // (-1: every replica; default 64: the large typed tables, where the F rounds bound the step)
     ma.prune_t = (int)variant("hprune", 64);
@@ -2847,14 +2798,14 @@ static ksim_hmemo::HMemoArgs hmemo_args(ksim_engine* e, int first, int stride) {
 
 // started: the residency gate's flags (K = 1 only); *gated tells the caller whether the launch carries them --
 // not when its Rg workgroups cannot all be resident at once (a gate that could never open)
-static int launch_hmemo(ksim_engine* e, int Rg, int first, int max_ev, hipStream_t st, int* started = nullptr,
-                        int gate_epoch = 0, bool* gated = nullptr) {
+static int launch_hmemo(ksim_engine* e, const RunEnv& env, int Rg, int first, int max_ev, hipStream_t st,
+                        int* started = nullptr, int gate_epoch = 0, bool* gated = nullptr) {
   using namespace ksim_hmemo;
   const HPlan& pl = *e->hplan;
   const int stride = std::max(max_ev, 1);
   int irc = hmemo_init_keys(e, Rg, first, st, 0);
   if (irc) return irc;
-  HMemoArgs ma = hmemo_args(e, first, stride);
+  HMemoArgs ma = hmemo_args(e, env, first, stride);
   ma.started = pl.K == 1 ? started : nullptr;
   ma.gate_epoch = gate_epoch;
   if (gated) *gated = false;
@@ -2862,19 +2813,18 @@ static int launch_hmemo(ksim_engine* e, int Rg, int first, int max_ev, hipStream
   for (const int r : e->hplan_reps) any_delete = any_delete || e->has_delete[r];  // the FGD replicas
   if (pl.K > 1) {
     if (any_delete) {
-      int rc = ensure_buf(e->d_h_hist, e->h_cap[13], (size_t)Rg * pl.K * stride);
+      int rc = e->d_h_hist.ensure((size_t)Rg * pl.K * stride);
       if (rc) return rc;
-      ma.hist = e->d_h_hist;
+      ma.hist = e->d_h_hist.p;
     }
     KSIM_HIP(hipMemsetAsync(e->d_gran, 0, sizeof(unsigned long long) * (size_t)Rg * 2 * pl.K * 2, st));
   }
-  const char* pe = std::getenv("KSIM_PROFILE");
-  const bool profile = pe && pe[0] == '1';
+  const bool profile = env.timers();
   if (profile) {
-    int rc = ensure_buf(e->d_h_prof, e->h_cap[12], (size_t)Rg * pl.K * kHProf);
+    int rc = e->d_h_prof.ensure((size_t)Rg * pl.K * kHProf);
     if (rc) return rc;
-    KSIM_HIP(hipMemsetAsync(e->d_h_prof, 0, sizeof(unsigned long long) * (size_t)Rg * pl.K * kHProf, st));
-    ma.prof = e->d_h_prof;
+    KSIM_HIP(hipMemsetAsync(e->d_h_prof.p, 0, sizeof(unsigned long long) * (size_t)Rg * pl.K * kHProf, st));
+    ma.prof = e->d_h_prof.p;
   }
   const bool gen = profile || ma.delay != 0;  // the general instantiation: timers, stress delays
   // the large-table instantiations (per-model tables of typed replicas, the F-list pruning) when a replica of
@@ -2903,7 +2853,7 @@ static int launch_hmemo(ksim_engine* e, int Rg, int first, int max_ev, hipStream
     KSIM_HIP(hipStreamSynchronize(st));
     const int nwg = Rg * pl.K;
     std::vector<unsigned long long> h((size_t)nwg * kHProf);
-    KSIM_HIP(hipMemcpy(h.data(), e->d_h_prof, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
+    KSIM_HIP(hipMemcpy(h.data(), e->d_h_prof.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
     // waves 1-15 (the bulk: every class but the event's own): 0 + 2 on the F waves, 4 on the class
     // waves beside them, then 3; wave 0: 1 (the own class's refresh, the critical path), 5 (the rest of
     // its step: decide + Bind, then the end-of-step barrier)
@@ -3110,14 +3060,15 @@ void ksim_engine_destroy(ksim_engine* e) {
   for (auto p : e->d_snap) (void)hipFree(p);
   for (auto p : e->d_prev) (void)hipFree(p);
   for (auto p : e->d_rep) (void)hipFree(p);
-  void* bufs[] = {e->d_nodes, e->d_tags, e->d_nodes_init, e->d_tags_init, e->d_tp, e->d_acc, e->d_reps, e->d_base, e->d_scratch,
-                  e->d_pod, e->d_res1, e->d_feas, e->d_score, e->d_gpu, e->d_gran, e->d_hist, e->d_fail, e->d_prof, e->d_replist,
-                  e->d_cap, e->d_mcap, e->d_last, e->d_send, e->d_recv, e->d_ptrs, e->d_m_pod, e->d_m_owner, e->d_m_wgcls,
-                  e->d_m_wgref, e->d_m_wggrp, e->d_win, e->d_m_evo, e->d_th, e->d_pw, e->d_cpum, e->d_pws,
-                  e->d_m_evcls, e->d_topg, e->d_m_hkeys, e->d_m_wgmap, e->d_h_cg, e->d_h_cls, e->d_h_cgrp, e->d_h_gpod, e->d_h_evc, e->d_h_st,
-                  e->d_h_ns, e->d_h_nstate, e->d_h_gsc, e->d_h_mtoff, e->d_h_mtab, e->d_h_na, e->d_h_keys, e->d_h_l1, e->d_h_l2, e->d_h_cnt, e->d_h_prof,
-                  e->d_h_hist, e->d_go, e->d_ggran, e->d_hgargs, e->d_rgran, e->d_rgreps, e->d_rglist, e->d_done, e->d_ragg};
-  for (void* p : bufs) (void)hipFree(p);
+  // the plain pointers and the growable buffers, in the order they were always freed in
+  release_all(e->d_nodes, e->d_tags, e->d_nodes_init, e->d_tags_init, e->d_tp, e->d_acc, e->d_reps, e->d_base,
+              e->d_scratch, e->d_pod, e->d_res1, e->d_feas, e->d_score, e->d_gpu, e->d_gran, e->d_hist, e->d_fail,
+              e->d_prof, e->d_replist, e->d_cap, e->d_mcap, e->d_last, e->d_send, e->d_recv, e->d_ptrs, e->d_m_pod,
+              e->d_m_owner, e->d_m_wgcls, e->d_m_wgref, e->d_m_wggrp, e->d_win, e->d_m_evo, e->d_th, e->d_pw,
+              e->d_cpum, e->d_pws, e->d_m_evcls, e->d_topg, e->d_m_hkeys, e->d_m_wgmap, e->d_h_cg, e->d_h_cls,
+              e->d_h_cgrp, e->d_h_gpod, e->d_h_evc, e->d_h_st, e->d_h_ns, e->d_h_nstate, e->d_h_gsc, e->d_h_mtoff,
+              e->d_h_mtab, e->d_h_na, e->d_h_keys, e->d_h_l1, e->d_h_l2, e->d_h_cnt, e->d_h_prof, e->d_h_hist,
+              e->d_go, e->d_ggran, e->d_hgargs, e->d_rgran, e->d_rgreps, e->d_rglist, e->d_done, e->d_ragg);
   for (int i = 0; i < ksim_engine::kSide; ++i) {
     if (e->side[i]) (void)hipStreamDestroy(e->side[i]);
     if (e->side_ev[i]) (void)hipEventDestroy(e->side_ev[i]);
@@ -3608,17 +3559,13 @@ static int run_report(ksim_engine* e, int max_ev, hipStream_t st, const int* lis
   const int B = variant("report_parts", 1) != 0
                     ? std::min({ksim_rep::kScanPartsMax, (e->cus + R - 1) / R, max_ev / 2048}) : 1;
   if (B > 1) {
-    const size_t n = (size_t)e->R * ksim_rep::kScanPartsMax * 2 * ksim_rep::kFields;
-    if (n > e->ragg_cap) {
-      if (e->d_ragg) KSIM_HIP(hipFree(e->d_ragg));
-      KSIM_HIP(hipMalloc(&e->d_ragg, sizeof(__int128) * n));
-      e->ragg_cap = n;
-    }
+    const int rc = e->d_ragg.ensure((size_t)e->R * ksim_rep::kScanPartsMax * 2 * ksim_rep::kFields);
+    if (rc) return rc;
     hipLaunchKernelGGL(ksim_rep::k_report_part, dim3((unsigned)B, (unsigned)R), dim3(ksim_rep::kScanBlock), 0, st,
-                       (const ReplicaDev*)e->d_reps, (const TypDev*)e->d_tp, e->N, list, e->d_ragg);
+                       (const ReplicaDev*)e->d_reps, (const TypDev*)e->d_tp, e->N, list, e->d_ragg.p);
     KSIM_HIP(hipGetLastError());
     hipLaunchKernelGGL(ksim_rep::k_report_apply, dim3((unsigned)B, (unsigned)R), dim3(ksim_rep::kScanBlock), 0, st,
-                       (const ReplicaDev*)e->d_reps, e->N, list, (const __int128*)e->d_ragg);
+                       (const ReplicaDev*)e->d_reps, e->N, list, (const __int128*)e->d_ragg.p);
     KSIM_HIP(hipGetLastError());
     return KSIM_OK;
   }
@@ -3782,7 +3729,7 @@ static int build_graph(ksim_engine* e) {
 static void print_replay_profile(ksim_engine* e, int R, int K, int steps) {
   const int nb = R * K, P = ksim_replay::kProfPhases;
   std::vector<unsigned long long> h((size_t)nb * P);
-  if (hipMemcpy(h.data(), e->d_prof, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost) != hipSuccess) return;
+  if (hipMemcpy(h.data(), e->d_prof.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost) != hipSuccess) return;
   static const char* names[] = {"pod", "filter(+emit)", "fgd-eval", "fgd-final", "agg-sync", "poll", "commit+publish", "end-sync"};
   std::fprintf(stderr, "ksim profile: %d workgroups (K=%d), %d steps, us/step mean [max]:", nb, K, steps);
   for (int ph = 0; ph < 8; ++ph) {
@@ -3840,26 +3787,299 @@ static size_t replay_lds(int S, int pol, bool general) {  // S real slots + the 
   return ksim_replay::replay_layout(S, pol, general).total;
 }
 
-
 // The dead-class skip (k_memo, k_hmemo, k_scan1): on create-only streams a class that once found no
 // feasible node never finds one again (Filter is monotone in the resources a creation takes), so its
 // later events are decided without a scan.  Needs every replica create-only with class ids < 1024;
 // KSIM_VARIANT=skip=0 turns it off (A/B runs).
-static bool dead_skip(const ksim_engine* e, const std::vector<int>& reps) {
-  if (variant("skip", 1) == 0) return false;
+static bool dead_skip(const ksim_engine* e, const RunEnv& env, const std::vector<int>& reps) {
+  if (!env.skip) return false;
   for (int r : reps)
     if (e->has_delete[r] || e->h_cls[r].size() > 1024) return false;
   return true;
 }
 
-// One k_replay launch per policy present (the kernel is specialised on the policy);
-// launches of different policies run back to back on the engine stream.
+// Group kinds of a run beside the policies themselves
 constexpr int kPolRandomGo = 64;  // run_persistent's group id of the k_random_go replicas
 constexpr int kPolFgdH = 66;      // ... of the one-workgroup FGD replicas on k_hmemo beside wide ones on k_memo (split_fgd)
 
-// The residency gate's host-mapped start flags: n of them, and a fresh epoch the next launch stores into them.
-static int gate_flags(ksim_engine* e, int n, int** d_flags, int* epoch) {
-  if (n > e->started_cap) {
+static void note_kernel(ksim_engine* e, const char* name) {
+  for (size_t p = 0; p < e->last_kernels.size();) {  // each name once
+    size_t q = e->last_kernels.find('+', p);
+    if (q == std::string::npos) q = e->last_kernels.size();
+    if (e->last_kernels.compare(p, q - p, name) == 0) return;
+    p = q + 1;
+  }
+  if (!e->last_kernels.empty()) e->last_kernels += '+';
+  e->last_kernels += name;
+}
+
+// ---- the run plan: everything run_persistent decides, before it launches anything ----
+enum GroupKernel { kRunRandomGo, kRunScan1, kRunMemo, kRunHmemo, kRunReplay, kRunNone };
+
+struct PlanGroup {
+  int kind = 0;              // a policy, kPolFgdH, ksim_scan1::kPolMix or kPolRandomGo
+  int first = 0, count = 0;  // its replicas: RunPlan::order[first .. first + count)
+  GroupKernel kernel = kRunReplay;  // (kRunNone: an FGD group the required memoised kernel has no plan for)
+  int side = -1;             // its side stream's index; -1: the engine stream
+  int K = 1, S = 0;          // k_replay and k_scan1 groups: workgroups per replica, nodes per slice, dynamic LDS bytes
+  size_t lds = 0;            // (k_replay: a co-resident grid the device cannot hold is narrowed at launch)
+};
+
+struct RunPlan {
+  std::vector<int> order;  // the replicas in launch order (uploaded as d_replist)
+  std::vector<PlanGroup> groups;
+  bool any_delete = false, general = false;  // general: k_replay's instantiation with timers, report stores, deletes
+  bool concurrent = false;                   // the groups on side streams, else back to back on the engine stream
+  bool reg1 = false;                         // k_scan1 keeps the node records in VGPRs
+  int fgd_cus = 0;                           // CUs the FGD groups hold (a k_memo / k_hmemo workgroup fills a CU's registers)
+};
+
+// K, S and LDS bytes of a k_replay group: choose_wgs, then narrower slices until the layout fits in LDS (or cannot
+// be narrowed further: the launcher refuses a layout that still does not fit).  Returns choose_wgs' own K.
+static int replay_fit(const ksim_engine* e, bool general, PlanGroup& g) {
+  const int K0 = g.K = choose_wgs(e, g.count);
+  g.S = (e->N + g.K - 1) / g.K;
+  while (replay_lds(g.S, g.kind, general) > 160 * 1024 && g.K < ksim_replay::kMaxK && g.count * (g.K + 1) <= e->cus) {
+    ++g.K;
+    g.S = (e->N + g.K - 1) / g.K;
+  }
+  g.lds = replay_lds(g.S, g.kind, general);
+  return K0;
+}
+
+// The replicas ordered into groups: a split FGD run's two plans first, then one group per policy present, the
+// Random replicas on Go's stream last (one k_random_go workgroup each).
+static void plan_order(const ksim_engine* e, RunPlan& pl) {
+  auto add = [&](int kind, int count) {
+    PlanGroup g;
+    g.kind = kind;
+    g.count = count;
+    if (count) pl.groups.push_back(g);
+  };
+  if (e->split_fgd) {  // the wide FGD replicas (k_memo) first, then the one-workgroup ones (k_hmemo): the plans' orders
+    pl.order = e->mplan_reps;
+    pl.order.insert(pl.order.end(), e->hplan_reps.begin(), e->hplan_reps.end());
+    add(POL_FGD, (int)e->mplan_reps.size());
+    add(kPolFgdH, (int)e->hplan_reps.size());
+  }
+  for (int pol = e->split_fgd ? POL_BESTFIT : POL_FGD; pol <= POL_PWR_FGD; ++pol) {
+    int c = 0;
+    for (int r = 0; r < e->R; ++r)
+      if (e->reps[r].policy == pol && !go_random(e, r)) { pl.order.push_back(r); ++c; }
+    add(pol, c);
+  }
+  int c = 0;
+  for (int r = 0; r < e->R; ++r)
+    if (go_random(e, r)) { pl.order.push_back(r); ++c; }
+  add(kPolRandomGo, c);
+}
+
+// Each group's kernel (with the k_replay fit of those that have no other), and whether the groups run concurrently on
+// side streams: when every group is at ONE workgroup per replica (no cross-workgroup exchange, so no co-residency
+// needed; a paper-sweep group fills 170 of 256 CUs, the next group's workgroups take the rest).  A group needing K > 1,
+// a k_memo launch outside a split FGD run or the profile timers keep the launches back to back on the engine stream.
+static void plan_kernels(const ksim_engine* e, const RunEnv& env, RunPlan& pl) {
+  const bool profile = env.timers();
+  pl.concurrent = !profile && pl.groups.size() >= 2;
+  for (PlanGroup& g : pl.groups) {
+    const bool fgd = g.kind == POL_FGD && e->run_mode != 2;
+    if (g.kind == kPolRandomGo) {  // one workgroup per replica
+      g.kernel = kRunRandomGo;
+    } else if (fgd && e->mplan_ok) {  // (a split FGD run's wide group is launched first, behind its gate)
+      g.kernel = kRunMemo;
+      pl.concurrent = pl.concurrent && e->split_fgd;
+    } else if ((fgd || g.kind == kPolFgdH) && e->hplan_ok) {  // concurrent at one workgroup per replica
+      g.kernel = kRunHmemo;
+      pl.concurrent = pl.concurrent && (g.kind == kPolFgdH || e->hplan->K == 1);
+    } else {
+      const int K0 = replay_fit(e, pl.general, g);
+      if (g.kind != kPolFgdH) pl.concurrent = pl.concurrent && g.K == 1;
+      // one workgroup per replica, create-only, a cheap policy: the 256-thread k_scan1 (ksim_scan1.hpp)
+      const bool scan1 = K0 == 1 && !profile && !pl.any_delete && e->scan1 && e->N <= kMaxSlice &&
+                         scan1_fn(g.kind, e->report, pl.reg1) &&
+                         ksim_scan1::scan1_lds(e->N, g.kind, e->report, pl.reg1) <= 160 * 1024;
+      if ((fgd || g.kind == kPolFgdH) && e->run_mode >= 3 && e->run_mode <= 5) {
+        g.kernel = kRunNone;
+      } else if (scan1) {
+        g.kernel = kRunScan1;
+        g.K = 1;
+        g.S = e->N;
+        g.lds = ksim_scan1::scan1_lds(e->N, g.kind, e->report, pl.reg1);
+      }
+    }
+  }
+}
+
+// The cheap-policy groups a concurrent run would give one k_scan1 launch each become ONE k_scan1_mix launch (policy
+// per workgroup), its replicas longest stream first, where the first of them stood: the run then needs one side
+// stream beside the FGD group's, whatever the hardware-queue mapping of the process.
+static void plan_mix(const ksim_engine* e, const RunEnv& env, RunPlan& pl) {
+  if (!(pl.concurrent && !pl.any_delete && e->scan1 && e->N <= kMaxSlice && env.scan1_mix &&
+        ksim_scan1::scan1_lds(e->N, ksim_scan1::kPolMix, e->report, pl.reg1) <= 160 * 1024))
+    return;
+  std::vector<int> mix, norder;
+  std::vector<PlanGroup> ngroups;
+  int f = 0, at = -1, nmix = 0;
+  for (const PlanGroup& g : pl.groups) {
+    bool m = g.kind >= POL_BESTFIT && g.kind <= POL_RANDOM;
+    for (int j = f; m && j < f + g.count; ++j)
+      m = g.kind != POL_DOTPROD || e->reps[pl.order[j]].dpcfg == (DIM_MERGE | NORM_MAX << 4);
+    if (m) {
+      mix.insert(mix.end(), pl.order.begin() + f, pl.order.begin() + f + g.count);
+      if (at < 0) at = (int)ngroups.size();
+      ++nmix;
+    } else {
+      ngroups.push_back(g);
+      norder.insert(norder.end(), pl.order.begin() + f, pl.order.begin() + f + g.count);
+    }
+    f += g.count;
+  }
+  if (nmix < 2) return;
+  std::stable_sort(mix.begin(), mix.end(), [&](int x, int y) { return e->n_events[x] > e->n_events[y]; });
+  int off = 0;
+  for (int g = 0; g < at; ++g) off += ngroups[g].count;
+  norder.insert(norder.begin() + off, mix.begin(), mix.end());
+  PlanGroup mg;
+  mg.kind = ksim_scan1::kPolMix;
+  mg.count = (int)mix.size();
+  mg.kernel = kRunScan1;
+  mg.K = 1;
+  mg.S = e->N;
+  mg.lds = ksim_scan1::scan1_lds(e->N, ksim_scan1::kPolMix, e->report, pl.reg1);
+  ngroups.insert(ngroups.begin() + at, mg);
+  pl.order.swap(norder);
+  pl.groups.swap(ngroups);
+}
+
+// What a run launches, in which order, on which streams.  Decides only: no launch, no engine state changed.
+static RunPlan make_run_plan(const ksim_engine* e, const RunEnv& env) {
+  RunPlan pl;
+  for (int r = 0; r < e->R; ++r) pl.any_delete = pl.any_delete || e->has_delete[r];
+  pl.general = env.timers() || e->report || pl.any_delete;
+  pl.reg1 = e->scan1 == 2 && e->N <= ksim_scan1::kBlock * ksim_scan1::kRegSlots;
+  plan_order(e, pl);
+  plan_kernels(e, env, pl);
+  plan_mix(e, env, pl);
+  // The side streams share the process's hardware queues (GPU_MAX_HW_QUEUES, HIP's default 4), and two streams on one
+  // queue run their kernels one after the other.  So no more side streams than queues (RunEnv::side_streams): the first
+  // group (FGD on k_hmemo, the longest in a paper sweep) gets one to itself, the others take the rest round robin.  A
+  // split FGD run's wide k_memo group runs on the engine stream itself, which otherwise only waits: three groups then
+  // need two side streams (with three, two groups shared a queue: 64 -> 133 ms for a C4 share, profiles/r06/c4_wide/).
+  const int nq = env.side_streams, g_off = e->split_fgd ? 1 : 0;
+  int first = 0;
+  for (int gi = 0; gi < (int)pl.groups.size(); ++gi) {
+    PlanGroup& g = pl.groups[gi];
+    g.first = first;
+    first += g.count;
+    const int j = gi - g_off;
+    g.side = !pl.concurrent || j < 0 ? -1 : (j == 0 || nq == 1) ? 0 : 1 + (j - 1) % (nq - 1);
+    if (g.kind == kPolFgdH) pl.fgd_cus += g.count;
+    else if (g.kind == POL_FGD && e->run_mode != 2)
+      pl.fgd_cus += e->mplan_ok ? e->mplan->nwg : g.count * (e->hplan_ok ? e->hplan->K : 1);
+  }
+  return pl;
+}
+
+static hipStream_t group_stream(const ksim_engine* e, const PlanGroup& g) { return g.side < 0 ? e->stream : e->side[g.side]; }
+
+static std::vector<int> group_reps(const RunPlan& plan, const PlanGroup& g) {
+  return std::vector<int>(plan.order.begin() + g.first, plan.order.begin() + g.first + g.count);
+}
+
+// ---- the launchers: one per kernel family ----
+// The diagnostics of one replay launch (last_run_kernels, last_run_wgs, last_run_path): K <= 0 leaves the width,
+// replicas (nullable) is the kernel's replica counter.
+static void note_launch(ksim_engine* e, const char* name, int K, int* replicas, int Rg) {
+  note_kernel(e, name);
+  if (K > 0) e->last_K = K;
+  if (replicas) *replicas += Rg;
+}
+
+// The source states of the Random replicas on Go's stream, uploaded before anything of the run is enqueued.
+static int upload_go_states(ksim_engine* e, const RunPlan& plan) {
+  if (plan.groups.empty() || plan.groups.back().kind != kPolRandomGo) return KSIM_OK;
+  const size_t words = (size_t)e->R * ksim_random_go::kStateWords;
+  const int rc = e->d_go.ensure(words);
+  if (rc) return rc;
+  std::vector<unsigned long long> h(words, 0ull);
+  for (int r = 0; r < e->R; ++r)
+    if (go_random(e, r))
+      std::copy(e->go_state[r].begin(), e->go_state[r].end(), h.begin() + (size_t)r * ksim_random_go::kStateWords);
+  KSIM_HIP(hipMemcpyAsync(e->d_go.p, h.data(), sizeof(unsigned long long) * words, hipMemcpyHostToDevice, e->stream));
+  KSIM_HIP(hipStreamSynchronize(e->stream));  // h is a local
+  return KSIM_OK;
+}
+
+static int launch_random_go(ksim_engine* e, const PlanGroup& g, hipStream_t gs) {
+  ksim_random_go::RandGoArgs ga{e->d_reps, e->d_replist + g.first, e->d_go.p, e->N};
+  const bool in_lds = ksim_random_go::lds_bytes(e->N, true) <= 160 * 1024;
+  const size_t lds = ksim_random_go::lds_bytes(e->N, in_lds);
+  if (in_lds) {
+    KSIM_HIP(hipFuncSetAttribute((const void*)ksim_random_go::k_random_go<true>,
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(ksim_random_go::k_random_go<true>, dim3(g.count), dim3(ksim_random_go::kBlock), lds, gs, ga);
+  } else {
+    hipLaunchKernelGGL(ksim_random_go::k_random_go<false>, dim3(g.count), dim3(ksim_random_go::kBlock), lds, gs, ga);
+  }
+  KSIM_HIP(hipGetLastError());
+  note_launch(e, "k_random_go", 0, &e->last_rgo, g.count);
+  return KSIM_OK;
+}
+
+// The overlapped report (KSIM_VARIANT report_overlap=0 off): a cheap group with more replicas than the CUs the FGD
+// groups leave can hold at once runs in waves of workgroups, so its last replicas end well after its first ones; its
+// replicas then report one by one as each ends (k_report_overlap, behind the first group on that group's stream)
+// instead of all after the last one.  Sets up the queue the replay feeds; *overlapped: the group gets that report.
+static int overlap_queue(ksim_engine* e, const RunEnv& env, const RunPlan& plan, const PlanGroup& g, const void* f,
+                         hipStream_t gs, ksim_scan1::Scan1Args& sa, bool* overlapped) {
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, ksim_scan1::kBlock, g.lds) != hipSuccess) {
+    (void)hipGetLastError();
+    nb = 0;
+  }
+  // (KSIM_TEST report_overlap=1: whatever the size, for the parity tests)
+  if (!(nb > 0 && (g.count > std::max(0, e->cus - plan.fgd_cus) * nb || env.force_report_overlap))) return KSIM_OK;
+  bool grew = false;
+  const int rc = e->d_done.ensure(2 + (size_t)g.count, &grew);
+  if (rc) return rc;
+  if (grew) KSIM_HIP(hipMemset(e->d_done.p, 0, sizeof(unsigned long long) * (2 + (size_t)g.count)));
+  if (!e->ev_ovl) KSIM_HIP(hipEventCreateWithFlags(&e->ev_ovl, hipEventDisableTiming));
+  KSIM_HIP(hipMemsetAsync(e->d_done.p, 0, 2 * sizeof(unsigned long long), gs));  // tickets; entries keep epochs
+  KSIM_HIP(hipEventRecord(e->ev_ovl, gs));
+  *overlapped = true;
+  e->last_ovl += g.count;
+  e->done_epoch = e->done_epoch % 0x7fffffffu + 1;
+  sa.done = e->d_done.p;
+  sa.epoch = e->done_epoch;
+  return KSIM_OK;
+}
+
+// k_scan1 (one cheap policy) or k_scan1_mix (the policy per workgroup): one 256-thread workgroup per replica.
+static int launch_scan1(ksim_engine* e, const RunEnv& env, const RunPlan& plan, int gi, hipStream_t gs, bool* overlapped) {
+  using namespace ksim_scan1;
+  const PlanGroup& g = plan.groups[gi];
+  const bool mix = g.kind == kPolMix, reg = plan.reg1;
+  const void* f = !mix ? scan1_fn(g.kind, e->report, reg)
+                  : e->report ? (reg ? (const void*)k_scan1_mix<true, true> : (const void*)k_scan1_mix<true, false>)
+                              : (reg ? (const void*)k_scan1_mix<false, true> : (const void*)k_scan1_mix<false, false>);
+  Scan1Args sa{e->d_reps, e->d_replist + g.first, e->N, dead_skip(e, env, group_reps(plan, g)) ? 1 : 0, nullptr, 0};
+  KSIM_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
+  if (mix && plan.concurrent && e->report && gi > 0 && env.report_overlap) {
+    const int rc = overlap_queue(e, env, plan, g, f, gs, sa, overlapped);
+    if (rc) return rc;
+  }
+  void* params[] = {(void*)&sa};
+  KSIM_HIP(hipLaunchKernel(f, dim3(g.count), dim3(ksim_scan1::kBlock), params, g.lds, gs));
+  note_launch(e, mix ? "k_scan1_mix" : "k_scan1", 1, &e->last_scan1, g.count);
+  return KSIM_OK;
+}
+
+// A launch behind the residency gate (gate: asked for): fresh start flags for its n workgroups, launch(flags, epoch,
+// &gated), then the host waits until every workgroup has started -- unless the launch cleared `gated` (it could not
+// carry the flags).  The next group is launched after that, so none of its workgroups holds a CU these wait for.
+static int launch_gated(ksim_engine* e, bool gate, int n, const char* what,
+                        const std::function<int(int*, int, bool*)>& launch) {
+  if (gate && n > e->started_cap) {  // the host-mapped start flags, one per workgroup
     if (e->h_started) KSIM_HIP(hipHostFree(e->h_started));
     e->h_started = nullptr;
     KSIM_HIP(hipHostMalloc((void**)&e->h_started, sizeof(int) * (size_t)n, hipHostMallocMapped | hipHostMallocCoherent));
@@ -3867,14 +4087,14 @@ static int gate_flags(ksim_engine* e, int n, int** d_flags, int* epoch) {
     KSIM_HIP(hipHostGetDevicePointer((void**)&e->d_started, e->h_started, 0));
     e->started_cap = n;
   }
-  *d_flags = e->d_started;
-  *epoch = e->gate_epoch = (e->gate_epoch % 0x3fffffff) + 1;
-  return KSIM_OK;
-}
-
-// Wait until the n workgroups of the launch just made have stored `epoch` (bounded: past 2 s the gate gives up,
-// counts it and says so on stderr -- it orders work, it decides nothing).
-static void gate_wait(ksim_engine* e, int n, int epoch, const char* what) {
+  int* flags = gate ? e->d_started : nullptr;
+  const int epoch = gate ? (e->gate_epoch = (e->gate_epoch % 0x3fffffff) + 1) : 0;  // the launch stores it into them
+  bool gated = gate;
+  const int rc = launch(flags, epoch, &gated);
+  if (rc) return rc;
+  if (!gated) return KSIM_OK;
+  // wait until the n workgroups have stored the epoch (bounded: past 2 s the gate gives up, counts it and says so on
+  // stderr -- it orders work, it decides nothing)
   const auto t0 = std::chrono::steady_clock::now();
   volatile int* fl = e->h_started;
   if (e->last_gate == 0) e->last_gate = 1;
@@ -3889,458 +4109,235 @@ static void gate_wait(ksim_engine* e, int n, int epoch, const char* what) {
     }
     std::this_thread::yield();
   }
-}
-
-static void note_kernel(ksim_engine* e, const char* name) {
-  for (size_t p = 0; p < e->last_kernels.size();) {  // each name once
-    size_t q = e->last_kernels.find('+', p);
-    if (q == std::string::npos) q = e->last_kernels.size();
-    if (e->last_kernels.compare(p, q - p, name) == 0) return;
-    p = q + 1;
-  }
-  if (!e->last_kernels.empty()) e->last_kernels += '+';
-  e->last_kernels += name;
-}
-
-static int run_persistent(ksim_engine* e, int max_ev) {
-  std::vector<int> order;
-  std::vector<std::pair<int, int>> groups;  // (policy, count) in `order`
-  if (e->split_fgd) {  // the wide FGD replicas (k_memo) first, then the one-workgroup ones (k_hmemo): the plans' orders
-    order = e->mplan_reps;
-    order.insert(order.end(), e->hplan_reps.begin(), e->hplan_reps.end());
-    groups.push_back({POL_FGD, (int)e->mplan_reps.size()});
-    groups.push_back({kPolFgdH, (int)e->hplan_reps.size()});
-  }
-  for (int pol = e->split_fgd ? POL_BESTFIT : POL_FGD; pol <= POL_PWR_FGD; ++pol) {
-    int c = 0;
-    for (int r = 0; r < e->R; ++r)
-      if (e->reps[r].policy == pol && !go_random(e, r)) { order.push_back(r); ++c; }
-    if (c) groups.push_back({pol, c});
-  }
-  {  // Random on Go's stream: one k_random_go workgroup per replica, last
-    int c = 0;
-    for (int r = 0; r < e->R; ++r)
-      if (go_random(e, r)) { order.push_back(r); ++c; }
-    if (c) {
-      groups.push_back({kPolRandomGo, c});
-      const size_t words = (size_t)e->R * ksim_random_go::kStateWords;
-      if (words > e->go_cap) {
-        if (e->d_go) KSIM_HIP(hipFree(e->d_go));
-        KSIM_HIP(hipMalloc(&e->d_go, sizeof(unsigned long long) * words));
-        e->go_cap = words;
-      }
-      std::vector<unsigned long long> h(words, 0ull);
-      for (int r = 0; r < e->R; ++r)
-        if (go_random(e, r))
-          std::copy(e->go_state[r].begin(), e->go_state[r].end(), h.begin() + (size_t)r * ksim_random_go::kStateWords);
-      KSIM_HIP(hipMemcpyAsync(e->d_go, h.data(), sizeof(unsigned long long) * words, hipMemcpyHostToDevice, e->stream));
-      KSIM_HIP(hipStreamSynchronize(e->stream));  // h is a local
-    }
-  }
-  bool any_delete = false;
-  for (int r = 0; r < e->R; ++r) any_delete = any_delete || e->has_delete[r];
-  const char* pe = std::getenv("KSIM_PROFILE");
-  const bool profile = pe && pe[0] == '1';
-  int first = 0;
-  e->last_memo = 0;
-  e->last_hmemo = 0;
-  e->last_rgo = 0;
-  e->last_scan1 = 0;
-  e->last_launches = (int)groups.size();
-  e->last_streams = 0;
-  // Groups whose replicas each fit ONE workgroup (K = 1: no cross-workgroup exchange, so no
-  // co-residency needed) run concurrently on side streams: a paper-sweep group fills 170 of 256 CUs,
-  // the next group's workgroups take the rest.  Any group needing K > 1 (or a k_memo launch, or the
-  // profile timers) keeps the launches back to back on the engine stream.
-  bool concurrent = !profile && groups.size() >= 2;
-  const bool gen_any = profile || e->report || any_delete;
-  for (const auto& gp : groups) {
-    if (!concurrent) break;
-    if (gp.first == kPolRandomGo || gp.first == kPolFgdH) continue;  // one workgroup per replica
-    if (gp.first == POL_FGD && e->split_fgd) continue;  // the wide k_memo group, launched first behind its gate
-    if (gp.first == POL_FGD && e->run_mode != 2 && e->mplan_ok) { concurrent = false; break; }
-    if (gp.first == POL_FGD && e->run_mode != 2 && e->hplan_ok) {
-      if (e->hplan->K > 1) { concurrent = false; break; }  // a co-resident wide launch
-      continue;  // one workgroup per replica
-    }
-    int K = choose_wgs(e, gp.second);
-    int S = (e->N + K - 1) / K;
-    while (replay_lds(S, gp.first, gen_any) > 160 * 1024 && K < ksim_replay::kMaxK && gp.second * (K + 1) <= e->cus) {
-      ++K;
-      S = (e->N + K - 1) / K;
-    }
-    concurrent = K == 1;
-  }
-  // The cheap-policy groups a concurrent run would give one k_scan1 launch each become ONE k_scan1_mix
-  // launch (policy per workgroup), its replicas longest stream first: the run then needs one side stream
-  // beside the FGD group's, whatever the hardware-queue mapping of the process.
-  const bool reg1 = e->scan1 == 2 && e->N <= ksim_scan1::kBlock * ksim_scan1::kRegSlots;
-  if (concurrent && !any_delete && e->scan1 && e->N <= kMaxSlice && variant("scan1_mix", 1) != 0 &&
-      ksim_scan1::scan1_lds(e->N, ksim_scan1::kPolMix, e->report, reg1) <= 160 * 1024) {
-    std::vector<int> mix, norder;
-    std::vector<std::pair<int, int>> ngroups;
-    int f = 0, at = -1, nmix = 0;
-    for (const auto& gp : groups) {
-      bool m = gp.first >= POL_BESTFIT && gp.first <= POL_RANDOM;
-      for (int j = f; m && j < f + gp.second; ++j)
-        m = gp.first != POL_DOTPROD || e->reps[order[j]].dpcfg == (DIM_MERGE | NORM_MAX << 4);
-      if (m) {
-        mix.insert(mix.end(), order.begin() + f, order.begin() + f + gp.second);
-        if (at < 0) at = (int)ngroups.size();
-        ++nmix;
-      } else {
-        ngroups.push_back(gp);
-        norder.insert(norder.end(), order.begin() + f, order.begin() + f + gp.second);
-      }
-      f += gp.second;
-    }
-    if (nmix >= 2) {
-      std::stable_sort(mix.begin(), mix.end(), [&](int x, int y) { return e->n_events[x] > e->n_events[y]; });
-      int off = 0;
-      for (int g = 0; g < at; ++g) off += ngroups[g].second;
-      norder.insert(norder.begin() + off, mix.begin(), mix.end());
-      ngroups.insert(ngroups.begin() + at, {ksim_scan1::kPolMix, (int)mix.size()});
-      order.swap(norder);
-      groups.swap(ngroups);
-      e->last_launches = (int)groups.size();
-    }
-  }
-  KSIM_HIP(hipMemcpyAsync(e->d_replist, order.data(), sizeof(int) * order.size(), hipMemcpyHostToDevice, e->stream));
-  KSIM_HIP(hipMemsetAsync(e->d_fail, 0, sizeof(int), e->stream));
-  int gidx = 0;
-  // The side streams share the process's hardware queues (GPU_MAX_HW_QUEUES, HIP's default 4), and two
-  // streams on one queue run their kernels one after the other.  So no more side streams than queues:
-  // the first group (FGD on k_hmemo, the longest in a paper sweep) gets one to itself, the others take
-  // the rest round robin (the engine stream, which only waits meanwhile, shares a queue with one of them).
-  int nq = 4;
-  if (const char* q = std::getenv("GPU_MAX_HW_QUEUES")) nq = std::atoi(q) > 0 ? std::atoi(q) : nq;
-  if (const char* q = std::getenv("KSIM_SIDE_STREAMS")) nq = std::atoi(q) > 0 ? std::atoi(q) : nq;
-  nq = std::max(1, std::min(nq, (int)ksim_engine::kSide));
-  unsigned used = 0u;
-  // Stream of concurrent group g: a side stream each (the first one alone on its own, the rest round robin), except
-  // that a split FGD run's wide k_memo group runs on the engine stream itself -- which otherwise only waits -- so the
-  // run needs one stream fewer: three groups on the engine stream and two side streams, within the hardware queues a
-  // process gets (with three side streams two groups shared a queue and ran one after the other: 64 -> 133 ms for a
-  // C4 share, profiles/r06/c4_wide/)
-  const int g_off = concurrent && e->split_fgd ? 1 : 0;
-  auto side_of = [&](int g) {
-    const int j = g - g_off;
-    return j < 0 ? -1 : (j == 0 || nq == 1) ? 0 : 1 + (j - 1) % (nq - 1);
-  };
-  if (concurrent) {
-    if (!e->ev_fork) KSIM_HIP(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-    KSIM_HIP(hipEventRecord(e->ev_fork, e->stream));
-    const char* gt0 = std::getenv("KSIM_GROUP_TIMES");
-    if (gt0 && gt0[0] == '1') {
-      if (!e->tev_fork) KSIM_HIP(hipEventCreate(&e->tev_fork));
-      KSIM_HIP(hipEventRecord(e->tev_fork, e->stream));
-    }
-  }
-  // The overlapped report (KSIM_VARIANT report_overlap=0 off): a cheap group with more replicas than the CUs the FGD
-  // groups leave can hold at once runs in waves of workgroups, so its last replicas end well after its first ones; its
-  // replicas then report one by one as each ends (k_report_overlap, behind the first group on that group's stream)
-  // instead of all after the last one.  ovl[g]: the group gets the queue and that report.
-  std::vector<char> ovl(groups.size(), 0);
-  int fgd_cus = 0;  // CUs the FGD groups hold (a k_memo / k_hmemo workgroup fills a CU's registers)
-  for (const auto& gp : groups) {
-    if (gp.first == kPolFgdH) fgd_cus += gp.second;
-    else if (gp.first == POL_FGD && e->run_mode != 2)
-      fgd_cus += e->mplan_ok ? e->mplan->nwg : gp.second * (e->hplan_ok ? e->hplan->K : 1);
-  }
-  unsigned ovl_epoch = 0;
-  for (const auto& gp : groups) {
-    const int Rg = gp.second;
-    hipStream_t gs = e->stream;
-    if (concurrent && side_of(gidx) >= 0) {
-      const int i = side_of(gidx);
-      if (!e->side[i]) {
-        KSIM_HIP(hipStreamCreateWithFlags(&e->side[i], hipStreamNonBlocking));
-        KSIM_HIP(hipEventCreateWithFlags(&e->side_ev[i], hipEventDisableTiming));
-      }
-      gs = e->side[i];
-      if (!(used & (1u << i))) KSIM_HIP(hipStreamWaitEvent(gs, e->ev_fork, 0));
-      used |= 1u << i;
-    }
-    ++gidx;
-    if (gp.first == kPolRandomGo) {
-      ksim_random_go::RandGoArgs ga{e->d_reps, e->d_replist + first, e->d_go, e->N};
-      const bool in_lds = ksim_random_go::lds_bytes(e->N, true) <= 160 * 1024;
-      const size_t lds = ksim_random_go::lds_bytes(e->N, in_lds);
-      if (in_lds) {
-        KSIM_HIP(hipFuncSetAttribute((const void*)ksim_random_go::k_random_go<true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(ksim_random_go::k_random_go<true>, dim3(Rg), dim3(ksim_random_go::kBlock), lds, gs, ga);
-      } else {
-        hipLaunchKernelGGL(ksim_random_go::k_random_go<false>, dim3(Rg), dim3(ksim_random_go::kBlock), lds, gs, ga);
-      }
-      KSIM_HIP(hipGetLastError());
-      note_kernel(e, "k_random_go");
-      e->last_groups = (int)groups.size();
-      e->last_rgo += Rg;
-      first += Rg;
-      continue;
-    }
-    if (gp.first == ksim_scan1::kPolMix) {
-      using namespace ksim_scan1;
-      const void* f = e->report ? (reg1 ? (const void*)k_scan1_mix<true, true> : (const void*)k_scan1_mix<true, false>)
-                                : (reg1 ? (const void*)k_scan1_mix<false, true> : (const void*)k_scan1_mix<false, false>);
-      const size_t lds = ksim_scan1::scan1_lds(e->N, ksim_scan1::kPolMix, e->report, reg1);
-      ksim_scan1::Scan1Args sa{e->d_reps, e->d_replist + first, e->N,
-                               dead_skip(e, std::vector<int>(order.begin() + first, order.begin() + first + Rg)) ? 1 : 0,
-                               nullptr, 0};
-      KSIM_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      if (concurrent && e->report && gidx > 1 && variant("report_overlap", 1) != 0) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, ksim_scan1::kBlock, lds) != hipSuccess) {
-          (void)hipGetLastError();
-          nb = 0;
-        }
-        // (KSIM_TEST report_overlap=1: whatever the size, for the parity tests)
-        if (nb > 0 && (Rg > std::max(0, e->cus - fgd_cus) * nb || test_knob("report_overlap", 0) != 0)) {
-          if (Rg > e->done_cap) {
-            if (e->d_done) KSIM_HIP(hipFree(e->d_done));
-            KSIM_HIP(hipMalloc(&e->d_done, sizeof(unsigned long long) * (2 + (size_t)Rg)));
-            KSIM_HIP(hipMemset(e->d_done, 0, sizeof(unsigned long long) * (2 + (size_t)Rg)));
-            e->done_cap = Rg;
-          }
-          if (!e->ev_ovl) KSIM_HIP(hipEventCreateWithFlags(&e->ev_ovl, hipEventDisableTiming));
-          KSIM_HIP(hipMemsetAsync(e->d_done, 0, 2 * sizeof(unsigned long long), gs));  // tickets; entries keep epochs
-          KSIM_HIP(hipEventRecord(e->ev_ovl, gs));
-          ovl[gidx - 1] = 1;
-          e->last_ovl += Rg;
-          ovl_epoch = e->done_epoch = e->done_epoch % 0x7fffffffu + 1;
-          sa.done = e->d_done;
-          sa.epoch = ovl_epoch;
-        }
-      }
-      void* params[] = {(void*)&sa};
-      KSIM_HIP(hipLaunchKernel(f, dim3(Rg), dim3(ksim_scan1::kBlock), params, lds, gs));
-      note_kernel(e, "k_scan1_mix");
-      e->last_K = 1;
-      e->last_groups = (int)groups.size();
-      e->last_scan1 += Rg;
-      first += Rg;
-      continue;
-    }
-    // FGD: the memoised replay when the cluster and the classes fit (run_mode 0 / 3)
-    if (gp.first == POL_FGD && e->run_mode != 2) {
-      if (e->mplan_ok) {  // prepared by prepare_memo (the FGD replicas are the first group of `order`)
-        const MemoPlan& pl = *e->mplan;
-        // a concurrent run (split_fgd): on its side stream, the next group launched once all Rg x K workgroups
-        // have started (the gate; without it the later groups' workgroups could hold the CUs a wide replica's
-        // exchange waits on)
-        const bool gate = concurrent && gidx < (int)groups.size();
-        int* flags = nullptr;
-        int epoch = 0;
-        if (gate) {
-          const int rc = gate_flags(e, pl.nwg, &flags, &epoch);
-          if (rc) return rc;
-        }
-        const int rc = launch_memo(e, pl, Rg, first, max_ev, gs, flags, epoch);
-        if (rc) return rc;
-        if (gate) gate_wait(e, pl.nwg, epoch, "FGD k_memo");
-        note_kernel(e, pl.hkeys ? "k_memo_hkeys" : "k_memo");
-        e->last_K = pl.K;
-        e->last_groups = (int)groups.size();
-        e->last_memo += Rg;
-        first += Rg;
-        if (profile) std::fprintf(stderr, "ksim memo%s: %d replicas, K=%d, Cw=%d, F waves %d, LDS %zu B\n",
-                                  pl.decider ? " (decider)" : "", Rg, pl.K, pl.Cw, pl.nfw, pl.lds);
-        continue;
-      }
-    }
-    if ((gp.first == POL_FGD && e->run_mode != 2) || gp.first == kPolFgdH) {
-      if (e->hplan_ok) {  // k_hmemo: one workgroup per replica, keys in HBM
-        // The residency gate (concurrent groups behind a K = 1 FGD group; KSIM_VARIANT gate=0 off): the long FGD
-        // replays take their CUs before any short group's workgroup is dispatched, so none of them waits
-        // for a CU that short replays hold.  The host waits for every workgroup's start flag (bounded: a
-        // gate that does not open in 2 s lets the launches go on, it orders work, it decides nothing).
-        const bool gate = concurrent && gidx < (int)groups.size() && e->hplan->K == 1 && variant("gate", 1) != 0;
-        int* flags = nullptr;
-        int epoch = 0;
-        if (gate) {
-          const int rc = gate_flags(e, Rg, &flags, &epoch);
-          if (rc) return rc;
-        }
-        bool gated = false;
-        const int rc = launch_hmemo(e, Rg, first, max_ev, gs, flags, epoch, &gated);
-        if (rc) return rc;
-        if (gated) gate_wait(e, Rg, epoch, "FGD k_hmemo");
-        note_kernel(e, e->hplan->K == 1 ? "k_hmemo" : "k_hmemo_wide");
-        e->last_K = e->hplan->K;
-        e->last_groups = (int)groups.size();
-        e->last_hmemo += Rg;
-        first += Rg;
-        continue;
-      }
-      if (e->run_mode >= 3 && e->run_mode <= 5) return KSIM_ENOTSUP;
-    }
-    int K = choose_wgs(e, Rg);
-    int S = (e->N + K - 1) / K;
-    const bool general = profile || e->report || any_delete;
-    // one workgroup per replica, create-only, a cheap policy: the 256-thread k_scan1 (ksim_scan1.hpp)
-    const bool reg = reg1;
-    if (K == 1 && !profile && !any_delete && e->scan1 && e->N <= kMaxSlice && scan1_fn(gp.first, e->report, reg) &&
-        ksim_scan1::scan1_lds(e->N, gp.first, e->report, reg) <= 160 * 1024) {
-      const void* f = scan1_fn(gp.first, e->report, reg);
-      const size_t lds = ksim_scan1::scan1_lds(e->N, gp.first, e->report, reg);
-      ksim_scan1::Scan1Args sa{e->d_reps, e->d_replist + first, e->N,
-                               dead_skip(e, std::vector<int>(order.begin() + first, order.begin() + first + Rg)) ? 1 : 0,
-                               nullptr, 0};
-      KSIM_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      void* params[] = {(void*)&sa};
-      KSIM_HIP(hipLaunchKernel(f, dim3(Rg), dim3(ksim_scan1::kBlock), params, lds, gs));
-      note_kernel(e, "k_scan1");
-      e->last_K = 1;
-      e->last_groups = (int)groups.size();
-      e->last_scan1 += Rg;
-      first += Rg;
-      continue;
-    }
-    while (replay_lds(S, gp.first, general) > 160 * 1024 && K < ksim_replay::kMaxK && Rg * (K + 1) <= e->cus) {
-      ++K;
-      S = (e->N + K - 1) / K;
-    }
-    if (replay_lds(S, gp.first, general) > 160 * 1024) return KSIM_ERANGE;
-    if (K > 1) {
-      // the occupancy query bounds the co-resident grid: fewer, larger slices when it is short
-      const int cap = resident_cap(e, replay_kernel(gp.first, K, general), replay_lds(S, gp.first, general));
-      if (Rg * K > cap) {
-        if (e->wgs_req > 0 && cap < Rg) return KSIM_ERANGE;
-        K = std::max(1, std::min(K, cap / Rg));
-        S = (e->N + K - 1) / K;
-        if (replay_lds(S, gp.first, general) > 160 * 1024) {
-          std::fprintf(stderr, "ksim: k_replay needs %d co-resident workgroups; the device holds %d\n", Rg * K, cap);
-          return KSIM_ERANGE;
-        }
-      }
-    }
-    const size_t need = any_delete ? (size_t)e->R * K * std::max(max_ev, 1) : 0;
-    if (need > e->hist_cap) {
-      if (e->d_hist) KSIM_HIP(hipFree(e->d_hist));
-      KSIM_HIP(hipMalloc(&e->d_hist, sizeof(int2) * need));
-      e->hist_cap = need;
-    }
-    size_t lds = replay_lds(S, gp.first, general);
-    // PWR+FGD: the per-(class, slot) memo when every class of the group fits beside the slice
-    // (KSIM_VARIANT pf_memo=0: evaluate every slot every step, as before r04)
-    int pm_c = 0;
-    if (gp.first == POL_PWR_FGD) {
-      if (variant("pf_memo", 1) != 0) {
-        for (int j = first; j < first + Rg; ++j) pm_c = std::max(pm_c, (int)e->h_cls[order[j]].size());
-        const size_t lm = ksim_replay::replay_layout(S, gp.first, general, pm_c).total;
-        if (pm_c > 0 && lm <= 160 * 1024 &&
-            (K == 1 || resident_cap(e, replay_kernel(gp.first, K, general), lm) >= Rg * K))
-          lds = lm;
-        else
-          pm_c = 0;
-      }
-    }
-    e->last_pf_memo = pm_c;
-    ksim_replay::ReplayArgs ra;
-    ra.xK = 0;
-    ra.group = 0;
-    ra.pm_c = pm_c;
-    {
-      const long v = test_knob("pf_memo_ver0", 0);
-      ra.pm_ver0 = v > 0 && v < (long)ksim_replay::kPmInvalid ? (unsigned)v : 0u;
-      ra.pf_guess = test_knob("pf_guess", 1) != 0 ? 1 : 0;
-    }
-    ra.reps = e->d_reps;
-    ra.rep_list = e->d_replist + first;
-    ra.N = e->N;
-    ra.K = K;
-    ra.S = S;
-    ra.gran = e->d_gran;
-    ra.hist = any_delete ? e->d_hist : nullptr;
-    ra.hist_stride = std::max(max_ev, 1);
-    ra.fail = e->d_fail;
-    ra.prof = nullptr;
-    ra.skip = dead_skip(e, std::vector<int>(order.begin() + first, order.begin() + first + Rg)) ? 1 : 0;
-    if (profile) {
-      const size_t words = (size_t)Rg * K * ksim_replay::kProfPhases;
-      if (words > e->prof_cap) {
-        if (e->d_prof) KSIM_HIP(hipFree(e->d_prof));
-        KSIM_HIP(hipMalloc(&e->d_prof, sizeof(unsigned long long) * words));
-        e->prof_cap = words;
-      }
-      KSIM_HIP(hipMemsetAsync(e->d_prof, 0, sizeof(unsigned long long) * words, e->stream));
-      ra.prof = e->d_prof;
-    }
-    // re-initialise every polled word before the launch (granule tags restart at step 1; K = 1 polls none)
-    if (K > 1)
-      KSIM_HIP(hipMemsetAsync(e->d_gran, 0,
-                              sizeof(unsigned long long) * (size_t)e->R * 2 * ksim_replay::kMaxK * ksim_replay::kGranW,
-                              e->stream));
-    const int grid = Rg * K;
-    const TypDev* tp = e->d_tp;
-    const int lrc = launch_persistent(replay_kernel(gp.first, K, general), grid, ksim_replay::kRBlock, lds, gs, e->coop && K > 1, ra, tp);
-    if (lrc) return lrc;
-    note_kernel(e, "k_replay");
-    e->last_K = K;
-    e->last_groups = (int)groups.size();
-    first += Rg;
-    if (profile) {
-      // phase timers of this group (the stream is in order; read back before the next group reuses them)
-      KSIM_HIP(hipStreamSynchronize(e->stream));
-      print_replay_profile(e, Rg, K, max_ev);
-    }
-  }
-  if (concurrent && e->report) {
-    // each group's report on its own stream, behind its replay: the groups that finish early report while
-    // the longest still runs; a timing event pair around each (last_report_ms sums them)
-    int f = 0;
-    if (e->grp_rev.size() < 2 * groups.size()) {
-      const size_t had = e->grp_rev.size();
-      e->grp_rev.resize(2 * groups.size(), nullptr);
-      for (size_t q = had; q < e->grp_rev.size(); ++q) KSIM_HIP(hipEventCreate(&e->grp_rev[q]));
-    }
-    for (size_t g = 0; g < groups.size(); ++g) {
-      const int Rg = groups[g].second;
-      const int i = side_of((int)g);
-      hipStream_t rs = i < 0 ? e->stream : e->side[i];
-      int mev = 0;
-      for (int j = f; j < f + Rg; ++j) mev = std::max(mev, e->n_events[order[j]]);
-      if (ovl[g]) {  // behind the first group on its stream, each replica's report as soon as its replay ends
-        const int i0 = side_of(0);
-        rs = i0 < 0 ? e->stream : e->side[i0];
-        KSIM_HIP(hipStreamWaitEvent(rs, e->ev_ovl, 0));
-      }
-      KSIM_HIP(hipEventRecord(e->grp_rev[2 * g], rs));
-      if (ovl[g]) {
-        hipLaunchKernelGGL(ksim_rep::k_report_overlap, dim3(std::min(Rg, std::max(1, e->cus - e->cus / 16))), dim3(ksim_rep::kScanBlock),
-                           0, rs, (const ReplicaDev*)e->d_reps, (const TypDev*)e->d_tp, e->N,
-                           (const int*)(e->d_replist + f), Rg, e->d_done, ovl_epoch, e->d_fail);
-        KSIM_HIP(hipGetLastError());
-      } else {
-        const int rc = run_report(e, mev, rs, e->d_replist + f, Rg);
-        if (rc) return rc;
-      }
-      KSIM_HIP(hipEventRecord(e->grp_rev[2 * g + 1], rs));
-      f += Rg;
-    }
-    e->grp_rev_used = (int)groups.size();
-    e->report_done = true;
-  }
-  e->tev_used = 0u;
-  const char* gt = std::getenv("KSIM_GROUP_TIMES");
-  if (concurrent && gt && gt[0] == '1') {
-    if (!e->tev_fork) KSIM_HIP(hipEventCreate(&e->tev_fork));
-    for (int i = 0; i < (int)ksim_engine::kSide; ++i) {
-      if (!(used & (1u << i))) continue;
-      if (!e->tev_side[i]) KSIM_HIP(hipEventCreate(&e->tev_side[i]));
-      KSIM_HIP(hipEventRecord(e->tev_side[i], e->side[i]));
-    }
-    e->tev_used = used;
-  }
-  e->last_streams = __builtin_popcount(used);
-  if (concurrent)  // join: the engine stream waits for every side stream used
-    for (int i = 0; i < (int)ksim_engine::kSide; ++i) {
-      if (!(used & (1u << i))) continue;
-      KSIM_HIP(hipEventRecord(e->side_ev[i], e->side[i]));
-      KSIM_HIP(hipStreamWaitEvent(e->stream, e->side_ev[i], 0));
-    }
   return KSIM_OK;
+}
+
+// k_memo for the planned FGD replicas (prepare_memo; they are the first group of the order).  In a concurrent run
+// (split_fgd) the next group is launched once all its workgroups have started: without the gate the later groups'
+// workgroups could hold the CUs a wide replica's exchange waits on.
+static int launch_memo_group(ksim_engine* e, const RunEnv& env, const RunPlan& plan, int gi, hipStream_t gs, int max_ev) {
+  const PlanGroup& g = plan.groups[gi];
+  const MemoPlan& pl = *e->mplan;
+  const bool gate = plan.concurrent && gi + 1 < (int)plan.groups.size();
+  const int rc = launch_gated(e, gate, pl.nwg, "FGD k_memo", [&](int* flags, int epoch, bool*) {
+    return launch_memo(e, env, pl, g.count, g.first, max_ev, gs, flags, epoch);
+  });
+  if (rc) return rc;
+  note_launch(e, pl.hkeys ? "k_memo_hkeys" : "k_memo", pl.K, &e->last_memo, g.count);
+  if (env.timers()) std::fprintf(stderr, "ksim memo%s: %d replicas, K=%d, Cw=%d, F waves %d, LDS %zu B\n",
+                                 pl.decider ? " (decider)" : "", g.count, pl.K, pl.Cw, pl.nfw, pl.lds);
+  return KSIM_OK;
+}
+
+// k_hmemo: the keys in HBM.  The residency gate (concurrent groups behind a K = 1 FGD group; KSIM_VARIANT gate=0 off):
+// the long FGD replays take their CUs before any short group's workgroup is dispatched, so none of them waits for
+// a CU that short replays hold.  The host waits for every workgroup's start flag (bounded: a gate that does not open
+// in 2 s lets the launches go on, it orders work, it decides nothing).
+static int launch_hmemo_group(ksim_engine* e, const RunEnv& env, const RunPlan& plan, int gi, hipStream_t gs, int max_ev) {
+  const PlanGroup& g = plan.groups[gi];
+  const int K = e->hplan->K;
+  const bool gate = plan.concurrent && gi + 1 < (int)plan.groups.size() && K == 1 && env.gate;
+  const int rc = launch_gated(e, gate, g.count, "FGD k_hmemo", [&](int* flags, int epoch, bool* gated) {
+    return launch_hmemo(e, env, g.count, g.first, max_ev, gs, flags, epoch, gated);
+  });
+  if (rc) return rc;
+  note_launch(e, K == 1 ? "k_hmemo" : "k_hmemo_wide", K, &e->last_hmemo, g.count);
+  return KSIM_OK;
+}
+
+// PWR+FGD: the per-(class, slot) memo when every class of the group fits beside the slice (KSIM_VARIANT pf_memo=0:
+// evaluate every slot every step, as before r04).  Returns the class stride (0: no memo) and the LDS bytes with it.
+static int replay_pf_memo(const ksim_engine* e, const RunEnv& env, const RunPlan& plan, const PlanGroup& g, int K, int S,
+                          size_t* lds) {
+  if (g.kind != POL_PWR_FGD || !env.pf_memo) return 0;
+  int pm_c = 0;
+  for (int j = g.first; j < g.first + g.count; ++j) pm_c = std::max(pm_c, (int)e->h_cls[plan.order[j]].size());
+  const size_t lm = ksim_replay::replay_layout(S, g.kind, plan.general, pm_c).total;
+  if (!(pm_c > 0 && lm <= 160 * 1024 &&
+        (K == 1 || resident_cap(e, replay_kernel(g.kind, K, plan.general), lm) >= g.count * K)))
+    return 0;
+  *lds = lm;
+  return pm_c;
+}
+
+// k_replay: one launch per policy (the kernel is specialised on it), K workgroups per replica.
+static int launch_replay(ksim_engine* e, const RunEnv& env, const RunPlan& plan, int gi, hipStream_t gs, int max_ev) {
+  const PlanGroup& g = plan.groups[gi];
+  const int pol = g.kind, Rg = g.count;
+  const bool general = plan.general, profile = env.timers();
+  int K = g.K, S = g.S;
+  if (g.lds > 160 * 1024) return KSIM_ERANGE;
+  if (K > 1) {
+    // the occupancy query bounds the co-resident grid: fewer, larger slices when it is short
+    const int cap = resident_cap(e, replay_kernel(pol, K, general), g.lds);
+    if (Rg * K > cap) {
+      if (e->wgs_req > 0 && cap < Rg) return KSIM_ERANGE;
+      K = std::max(1, std::min(K, cap / Rg));
+      S = (e->N + K - 1) / K;
+      if (replay_lds(S, pol, general) > 160 * 1024) {
+        std::fprintf(stderr, "ksim: k_replay needs %d co-resident workgroups; the device holds %d\n", Rg * K, cap);
+        return KSIM_ERANGE;
+      }
+    }
+  }
+  int rc;
+  if (plan.any_delete && (rc = e->d_hist.ensure((size_t)e->R * K * std::max(max_ev, 1)))) return rc;  // the bind history
+  size_t lds = replay_lds(S, pol, general);
+  ksim_replay::ReplayArgs ra;
+  ra.xK = 0;
+  ra.group = 0;
+  ra.pm_c = e->last_pf_memo = replay_pf_memo(e, env, plan, g, K, S, &lds);
+  ra.pm_ver0 = env.pf_memo_ver0 > 0 && env.pf_memo_ver0 < (long)ksim_replay::kPmInvalid ? (unsigned)env.pf_memo_ver0 : 0u;
+  ra.pf_guess = env.pf_guess ? 1 : 0;
+  ra.reps = e->d_reps;
+  ra.rep_list = e->d_replist + g.first;
+  ra.N = e->N;
+  ra.K = K;
+  ra.S = S;
+  ra.gran = e->d_gran;
+  ra.hist = plan.any_delete ? e->d_hist.p : nullptr;
+  ra.hist_stride = std::max(max_ev, 1);
+  ra.fail = e->d_fail;
+  ra.prof = nullptr;
+  ra.skip = dead_skip(e, env, group_reps(plan, g)) ? 1 : 0;
+  if (profile) {
+    const size_t words = (size_t)Rg * K * ksim_replay::kProfPhases;
+    if ((rc = e->d_prof.ensure(words))) return rc;
+    KSIM_HIP(hipMemsetAsync(e->d_prof.p, 0, sizeof(unsigned long long) * words, e->stream));
+    ra.prof = e->d_prof.p;
+  }
+  // re-initialise every polled word before the launch (granule tags restart at step 1; K = 1 polls none)
+  if (K > 1)
+    KSIM_HIP(hipMemsetAsync(e->d_gran, 0,
+                            sizeof(unsigned long long) * (size_t)e->R * 2 * ksim_replay::kMaxK * ksim_replay::kGranW,
+                            e->stream));
+  const TypDev* tp = e->d_tp;
+  rc = launch_persistent(replay_kernel(pol, K, general), Rg * K, ksim_replay::kRBlock, lds, gs, e->coop && K > 1, ra, tp);
+  if (rc) return rc;
+  note_launch(e, "k_replay", K, nullptr, Rg);
+  if (profile) {
+    // phase timers of this group (the stream is in order; read back before the next group reuses them)
+    KSIM_HIP(hipStreamSynchronize(e->stream));
+    print_replay_profile(e, Rg, K, max_ev);
+  }
+  return KSIM_OK;
+}
+
+// ---- a concurrent run's side streams ----
+// Fork: the side streams start behind this point of the engine stream (KSIM_GROUP_TIMES=1: a timing event there too).
+static int fork_streams(ksim_engine* e, const RunEnv& env) {
+  if (!e->ev_fork) KSIM_HIP(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
+  KSIM_HIP(hipEventRecord(e->ev_fork, e->stream));
+  if (env.group_times) {
+    if (!e->tev_fork) KSIM_HIP(hipEventCreate(&e->tev_fork));
+    KSIM_HIP(hipEventRecord(e->tev_fork, e->stream));
+  }
+  return KSIM_OK;
+}
+
+// The group's side stream, created on first use and put behind the fork the first time this run uses it.
+static int enter_side_stream(ksim_engine* e, const PlanGroup& g, unsigned* used) {
+  const int i = g.side;
+  if (i < 0) return KSIM_OK;
+  if (!e->side[i]) {
+    KSIM_HIP(hipStreamCreateWithFlags(&e->side[i], hipStreamNonBlocking));
+    KSIM_HIP(hipEventCreateWithFlags(&e->side_ev[i], hipEventDisableTiming));
+  }
+  if (!(*used & (1u << i))) KSIM_HIP(hipStreamWaitEvent(e->side[i], e->ev_fork, 0));
+  *used |= 1u << i;
+  return KSIM_OK;
+}
+
+// KSIM_GROUP_TIMES=1: a timing event at each used side stream's end (ksim_engine_run prints them).
+static int record_group_times(ksim_engine* e, const RunEnv& env, const RunPlan& plan, unsigned used) {
+  e->tev_used = 0u;
+  if (!plan.concurrent || !env.group_times) return KSIM_OK;
+  if (!e->tev_fork) KSIM_HIP(hipEventCreate(&e->tev_fork));
+  for (int i = 0; i < (int)ksim_engine::kSide; ++i) {
+    if (!(used & (1u << i))) continue;
+    if (!e->tev_side[i]) KSIM_HIP(hipEventCreate(&e->tev_side[i]));
+    KSIM_HIP(hipEventRecord(e->tev_side[i], e->side[i]));
+  }
+  e->tev_used = used;
+  return KSIM_OK;
+}
+
+// Join: the engine stream waits for every side stream used.
+static int join_streams(ksim_engine* e, unsigned used) {
+  for (int i = 0; i < (int)ksim_engine::kSide; ++i) {
+    if (!(used & (1u << i))) continue;
+    KSIM_HIP(hipEventRecord(e->side_ev[i], e->side[i]));
+    KSIM_HIP(hipStreamWaitEvent(e->stream, e->side_ev[i], 0));
+  }
+  return KSIM_OK;
+}
+
+// A concurrent run's reports: each group's on its own stream, behind its replay -- the groups that finish early
+// report while the longest still runs; a timing event pair around each (last_report_ms sums them).  ovl_group (-1:
+// none): the group whose replicas report one by one as each ends (overlap_queue), behind the first group on its stream.
+static int launch_group_reports(ksim_engine* e, const RunPlan& plan, int ovl_group) {
+  const size_t ng = plan.groups.size();
+  if (e->grp_rev.size() < 2 * ng) {
+    const size_t had = e->grp_rev.size();
+    e->grp_rev.resize(2 * ng, nullptr);
+    for (size_t q = had; q < e->grp_rev.size(); ++q) KSIM_HIP(hipEventCreate(&e->grp_rev[q]));
+  }
+  for (size_t gi = 0; gi < ng; ++gi) {
+    const PlanGroup& g = plan.groups[gi];
+    const bool ovl = (int)gi == ovl_group;
+    hipStream_t rs = group_stream(e, ovl ? plan.groups[0] : g);
+    int mev = 0;
+    for (int j = g.first; j < g.first + g.count; ++j) mev = std::max(mev, e->n_events[plan.order[j]]);
+    if (ovl) KSIM_HIP(hipStreamWaitEvent(rs, e->ev_ovl, 0));
+    KSIM_HIP(hipEventRecord(e->grp_rev[2 * gi], rs));
+    if (ovl) {
+      hipLaunchKernelGGL(ksim_rep::k_report_overlap, dim3(std::min(g.count, std::max(1, e->cus - e->cus / 16))),
+                         dim3(ksim_rep::kScanBlock), 0, rs, (const ReplicaDev*)e->d_reps, (const TypDev*)e->d_tp, e->N,
+                         (const int*)(e->d_replist + g.first), g.count, e->d_done.p, e->done_epoch, e->d_fail);
+      KSIM_HIP(hipGetLastError());
+    } else {
+      const int rc = run_report(e, mev, rs, e->d_replist + g.first, g.count);
+      if (rc) return rc;
+    }
+    KSIM_HIP(hipEventRecord(e->grp_rev[2 * gi + 1], rs));
+  }
+  e->grp_rev_used = (int)ng;
+  e->report_done = true;
+  return KSIM_OK;
+}
+
+// The persistent path: plan, upload the order, fork, launch each group, reports, join.
+static int run_persistent(ksim_engine* e, const RunEnv& env, int max_ev) {
+  const RunPlan plan = make_run_plan(e, env);
+  int rc = upload_go_states(e, plan);
+  if (rc) return rc;
+  e->last_memo = e->last_hmemo = e->last_rgo = e->last_scan1 = 0;
+  e->last_launches = (int)plan.groups.size();
+  KSIM_HIP(hipMemcpyAsync(e->d_replist, plan.order.data(), sizeof(int) * plan.order.size(), hipMemcpyHostToDevice, e->stream));
+  KSIM_HIP(hipMemsetAsync(e->d_fail, 0, sizeof(int), e->stream));
+  if (plan.concurrent && (rc = fork_streams(e, env))) return rc;
+  unsigned used = 0u;  // side streams the run has launched on
+  int ovl_group = -1;
+  for (int gi = 0; gi < (int)plan.groups.size(); ++gi) {
+    const PlanGroup& g = plan.groups[gi];
+    if ((rc = enter_side_stream(e, g, &used))) return rc;
+    hipStream_t gs = group_stream(e, g);
+    bool ovl = false;
+    switch (g.kernel) {
+      case kRunRandomGo: rc = launch_random_go(e, g, gs); break;
+      case kRunScan1: rc = launch_scan1(e, env, plan, gi, gs, &ovl); break;
+      case kRunMemo: rc = launch_memo_group(e, env, plan, gi, gs, max_ev); break;
+      case kRunHmemo: rc = launch_hmemo_group(e, env, plan, gi, gs, max_ev); break;
+      case kRunReplay: rc = launch_replay(e, env, plan, gi, gs, max_ev); break;
+      case kRunNone: rc = KSIM_ENOTSUP; break;
+    }
+    if (rc) return rc;
+    if (ovl) ovl_group = gi;
+  }
+  if (plan.concurrent && e->report && (rc = launch_group_reports(e, plan, ovl_group))) return rc;
+  if ((rc = record_group_times(e, env, plan, used))) return rc;
+  e->last_streams = __builtin_popcount(used);
+  return plan.concurrent ? join_streams(e, used) : KSIM_OK;
 }
 
 static int run_graph(ksim_engine* e, int max_ev) {
@@ -4360,6 +4357,7 @@ int ksim_engine_run(ksim_engine* e) {
     max_ev = std::max(max_ev, e->n_events[r]);
   }
   KSIM_HIP(hipSetDevice(e->device));
+  const RunEnv env = read_env();
   e->report_done = false;
   e->grp_rev_used = 0;
   e->tev_used = 0u;  // KSIM_GROUP_TIMES: only run_persistent's concurrent groups record side-stream ends
@@ -4382,9 +4380,9 @@ int ksim_engine_run(ksim_engine* e) {
     if (go_random(e, r) && (step_path || e->shard_world > 0 ||
                             (e->reps[r].gpusel != SEL_BEST && e->reps[r].gpusel != SEL_WORST && e->reps[r].gpusel != SEL_RANDOM)))
       return KSIM_ENOTSUP;
-  if (e->shard_world > 0 && !e->peers.empty()) rc = run_hmemo_peer(e, max_ev);
+  if (e->shard_world > 0 && !e->peers.empty()) rc = run_hmemo_peer(e, env, max_ev);
   else if (e->shard_world > 0) rc = any_pwr(e) ? KSIM_ENOTSUP : run_sharded(e, max_ev);
-  else rc = step_path ? run_graph(e, max_ev) : run_persistent(e, max_ev);
+  else rc = step_path ? run_graph(e, max_ev) : run_persistent(e, env, max_ev);
   if (!rc && e->shard_world > 0) note_kernel(e, !e->peers.empty() ? "k_hmemo_wide" : "k_step");
   if (!rc && step_path) note_kernel(e, any_pwr(e) ? "k_step+k_step_pwr" : "k_step");
   if (rc) return rc;
@@ -4591,7 +4589,7 @@ int ksim_engine_set_shard_peers(ksim_engine* e, const uint8_t* handles) {
 
 // ksim_engine_run of a shard with peers: k_hmemo over this shard's slices, the exchange spanning every
 // shard's workgroups (K per shard, the same K and S on every rank: from n_global and world only).
-static int run_hmemo_peer(ksim_engine* e, int max_ev) {
+static int run_hmemo_peer(ksim_engine* e, const RunEnv& env, int max_ev) {
   using namespace ksim_hmemo;
   if (e->R != 1 || e->reps[0].policy != POL_FGD || e->report || go_random(e, 0) || !score_table())
     return KSIM_ENOTSUP;
@@ -4617,7 +4615,7 @@ static int run_hmemo_peer(ksim_engine* e, int max_ev) {
   KSIM_HIP(hipMemcpyAsync(e->d_tags, e->d_tags_init, sizeof(uint16_t) * e->tags_stride, hipMemcpyDeviceToDevice, st));
   KSIM_HIP(hipMemsetAsync(e->d_res[0], 0xff, sizeof(ResultDev) * (size_t)stride, st));
   if ((rc = hmemo_init_keys(e, 1, 0, st, e->node_off))) return rc;
-  HMemoArgs a = hmemo_args(e, 0, stride);
+  HMemoArgs a = hmemo_args(e, env, 0, stride);
   a.roff = e->node_off;
   a.wbase = e->shard_rank * K;
   a.Ktot = Kt;
@@ -4628,8 +4626,8 @@ static int run_hmemo_peer(ksim_engine* e, int max_ev) {
   a.epoch = e->peer_epoch;
   for (int q = 0; q < world; ++q) a.peer[q] = e->peers[q];
   if (e->has_delete[0]) {
-    if ((rc = ensure_buf(e->d_h_hist, e->h_cap[13], (size_t)K * stride))) return rc;
-    a.hist = e->d_h_hist;
+    if ((rc = e->d_h_hist.ensure((size_t)K * stride))) return rc;
+    a.hist = e->d_h_hist.p;
   }
   KSIM_HIP(hipMemsetAsync(e->d_fail, 0, sizeof(int), st));
   const bool gen = a.delay != 0;
@@ -4678,7 +4676,7 @@ static bool hmemo_group_eligible(ksim_engine* const* engines, int world) {
 // selectHost over the union, generic_scheduler.go:187-212; BestFit's NormalizeScore range rides in the same granules
 // as in the unsharded k_replay, plugin_utils.go:48-74).  Lean runs only: one replica per shard,
 // a create-only stream, no report, no profile.
-static bool replay_group_eligible(ksim_engine* const* engines, int world) {
+static bool replay_group_eligible(ksim_engine* const* engines, int world, const RunEnv& env) {
   const int pol = engines[0]->reps[0].policy;
   if (pol < POL_BESTFIT || pol > POL_RANDOM || variant("shard_replay", 1) == 0) return false;
   for (int k = 0; k < world; ++k) {
@@ -4686,12 +4684,11 @@ static bool replay_group_eligible(ksim_engine* const* engines, int world) {
     if (e->R != 1 || e->reps[0].policy != pol || e->report || e->run_mode == 1 || e->has_delete[0] || go_random(e, 0))
       return false;
   }
-  const char* pe = std::getenv("KSIM_PROFILE");
-  return !(pe && pe[0] != '0');
+  return env.profile == 0;
 }
 
 // KSIM_OK with *done = false: the group does not fit (the caller keeps the per-pod k_step path).
-static int run_replay_group(ksim_engine* const* engines, int world, int max_ev, bool* done) {
+static int run_replay_group(ksim_engine* const* engines, int world, const RunEnv& env, int max_ev, bool* done) {
   using namespace ksim_replay;
   *done = false;
   ksim_engine* e0 = engines[0];
@@ -4730,7 +4727,7 @@ static int run_replay_group(ksim_engine* const* engines, int world, int max_ev, 
     KSIM_HIP(hipMemcpyAsync(e->d_tags, e->d_tags_init, sizeof(uint16_t) * e->tags_stride, hipMemcpyDeviceToDevice, st));
     KSIM_HIP(hipMemsetAsync(e->d_res[0], 0xff, sizeof(ResultDev) * (size_t)std::max(e->n_events[0], 1), st));
     KSIM_HIP(hipMemcpyAsync(e0->d_rgreps + k, e->d_reps, sizeof(ReplicaDev), hipMemcpyDeviceToDevice, st));
-    skip = skip && dead_skip(e, std::vector<int>{0});
+    skip = skip && dead_skip(e, env, std::vector<int>{0});
   }
   ReplayArgs ra;
   std::memset(&ra, 0, sizeof ra);
@@ -4771,7 +4768,7 @@ static int run_replay_group(ksim_engine* const* engines, int world, int max_ev, 
 }
 
 // KSIM_OK with *done = false: the group does not fit k_hmemo (the caller keeps the per-pod k_step path).
-static int run_hmemo_group(ksim_engine* const* engines, int world, int max_ev, bool* done) {
+static int run_hmemo_group(ksim_engine* const* engines, int world, const RunEnv& env, int max_ev, bool* done) {
   using namespace ksim_hmemo;
   *done = false;
   ksim_engine* e0 = engines[0];
@@ -4796,7 +4793,7 @@ static int run_hmemo_group(ksim_engine* const* engines, int world, int max_ev, b
     e->mplan_dirty = true;  // the unsharded plan is not this one
     lds = std::max(lds, e->hplan->lds);
   }
-  const bool gen = hdelay_mask() != 0;  // the hdelay test knob: the general instantiation
+  const bool gen = env.hdelay != 0;  // the hdelay test knob: the general instantiation
   const void* f = Kt <= 64 ? (gen ? (const void*)k_hmemo_group<1, true> : (const void*)k_hmemo_group<1, false>)
                            : (gen ? (const void*)k_hmemo_group<4, true> : (const void*)k_hmemo_group<4, false>);
   if (Kt > resident_cap(e0, f, lds)) return KSIM_OK;
@@ -4812,16 +4809,16 @@ static int run_hmemo_group(ksim_engine* const* engines, int world, int max_ev, b
     KSIM_HIP(hipMemsetAsync(e->d_res[0], 0xff, sizeof(ResultDev) * (size_t)std::max(e->n_events[0], 1), st));
     int rc = hmemo_init_keys(e, 1, 0, st, e->node_off);
     if (rc) return rc;
-    HMemoArgs a = hmemo_args(e, 0, stride);
+    HMemoArgs a = hmemo_args(e, env, 0, stride);
     a.roff = e->node_off;
     a.wbase = k * K;
     a.Ktot = Kt;
     a.gran = e0->d_ggran;
     a.fail = e0->d_fail;
     if (e->has_delete[0]) {
-      rc = ensure_buf(e->d_h_hist, e->h_cap[13], (size_t)K * stride);
+      rc = e->d_h_hist.ensure((size_t)K * stride);
       if (rc) return rc;
-      a.hist = e->d_h_hist;
+      a.hist = e->d_h_hist.p;
     }
     args[k] = a;
   }
@@ -4871,16 +4868,17 @@ int ksim_shard_group_run(ksim_engine* const* engines, int world) {
     max_ev = std::max(max_ev, e->n_events[0]);
   }
   KSIM_HIP(hipSetDevice(e0->device));
+  const RunEnv env = read_env();
   if (hmemo_group_eligible(engines, world)) {
     bool done = false;
-    const int rc = run_hmemo_group(engines, world, max_ev, &done);
+    const int rc = run_hmemo_group(engines, world, env, max_ev, &done);
     if (!rc && done)
       for (int k = 0; k < world; ++k) engines[k]->last_kernels = "k_hmemo_group";
     if (rc || done) return rc;
   }
-  if (replay_group_eligible(engines, world)) {
+  if (replay_group_eligible(engines, world, env)) {
     bool done = false;
-    const int rc = run_replay_group(engines, world, max_ev, &done);
+    const int rc = run_replay_group(engines, world, env, max_ev, &done);
     if (rc || done) return rc;
   }
   for (int k = 0; k < world; ++k) engines[k]->last_kernels = "k_step";
