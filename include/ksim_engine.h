@@ -390,6 +390,36 @@ int  ksim_engine_last_run_wgs(ksim_engine* e, int* wgs_per_replica);
 #define KSIM_PATH_SCAN1   7
 int  ksim_engine_last_run_path(ksim_engine* e, int* path);
 
+/* Fragmentation-aware descheduling (pkg/simulator/deschedule.go:20-47 DescheduleCluster; fragOnePod :94-119,
+ * fragMultiPod :121-178; the victim of one node: findVictimPodOnNodeFragAware, deschedule_utils.go:73-106).
+ * After a completed ksim_engine_run, ksim_engine_deschedule plans, on the device and for every replica, which
+ * bound pods to evict and in which order, from the run's results and final node records.  A pod is bound when
+ * it was scheduled and no later delete event removed it.  budget = ceil(ratio * bound pods), at most the bound
+ * pods.  Planning changes no cluster state and may be repeated with another policy or ratio after the same run;
+ * calls that change the cluster after the run (reserve / unreserve / bind / schedule) are not seen as pod
+ * events.  The victims are rescheduled by replaying the stream extended with their deletions and
+ * re-creations (ksim/desched.py).  Order contract where the reference's order is a Go map's: pods of a node
+ * in ascending creation-event index, nodes of equal priority by name_rank (DESIGN.md "Descheduling").
+ *   KSIM_EINVAL   bad policy, ratio < 0 or NaN         KSIM_ENOTSUP  node-sharded engine
+ *   KSIM_ESTATE   no completed run since the last set_nodes / set_typical / load_events
+ *   KSIM_ENODEV   no gfx950 device
+ * ksim_engine_get_victims: replica's victims in eviction order into out[cap]; *n_out their number (set even
+ * when cap is too small: KSIM_ERANGE), *budget_out (nullable) the budget.  KSIM_ESTATE before a plan.
+ * ksim_engine_last_deschedule_ms: device time of the last plan, its host step between the kernels included. */
+enum ksim_desched_policy { KSIM_DESCHED_FRAG_ONE_POD = 0, KSIM_DESCHED_FRAG_MULTI_POD = 1 };
+typedef struct {
+    int32_t event;        /* creation event index of the victim */
+    int32_t node;         /* node it is evicted from */
+    int32_t gpu_mask;     /* devices it held */
+    int32_t reserved;
+    int64_t score;        /* int64(frag_before - frag_after), > 0 */
+    double  frag_before;  /* the node's priority when it was picked */
+    double  frag_after;   /* F(node + pod): the node's next priority under fragMultiPod */
+} ksim_victim;            /* 40 bytes */
+int  ksim_engine_deschedule(ksim_engine* e, int policy, double ratio);
+int  ksim_engine_get_victims(ksim_engine* e, int replica, ksim_victim* out, int cap, int* n_out, int* budget_out);
+int  ksim_engine_last_deschedule_ms(ksim_engine* e, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,337 @@
+// ksim_desched.hpp -- fragmentation-aware descheduling on the device (planning only).
+//
+// After a trace has been scheduled the reference can evict the pods that cause the most GPU
+// fragmentation and schedule them again (pkg/simulator/deschedule.go:20-47 DescheduleCluster with the
+// policies fragOnePod :94-119 and fragMultiPod :121-178; the victim of one node is
+// findVictimPodOnNodeFragAware, deschedule_utils.go:73-106).  Here the plan -- which pods, in which
+// order -- is made on the device from the last run's results and final node records:
+//   k_desched_mark    one thread per event: a delete event that took effect marks its creation event;
+//   k_desched_eval    one thread per event: for a pod still bound, F(node) and F(node + pod)
+//                     (NodeResource.Add, pkg/type/resource.go:482-512), and the bound-pod count;
+//   k_desched_select  one workgroup per replica: the pop / pick / re-key loop of the policy over those
+//                     values, victims in eviction order.
+// The rescheduling itself is the ordinary replay of the extended event stream (ksim/desched.py).
+// No kernel here waits for another workgroup, and nothing is on the per-pod path.
+//
+// fragMultiPod passes the node state built BEFORE its loop on every pop (deschedule.go:124, :156:
+// nodeResMap is never updated), so the candidate states of a later pop of the same node are still
+// "the original node + one pod"; only the left-hand side of the score moves (the priority stored at
+// the previous eviction, :162-163).  F(original node + pod) is therefore computed once per bound pod
+// and the loop is pure selection.  Order contract (the reference's is a Go map's and an unstable
+// sort's): pods of a node in ascending creation-event index, nodes of equal priority by name rank.
+#pragma once
+
+#include "ksim_device.hpp"
+#include "ksim_engine.h"
+
+namespace ksim_ds {
+
+using namespace ksim;
+
+// NodeResource.Add(podRes, gpu ids) (resource.go:482-512) on a node state, then F of the result.
+// CPU left grows by PodResource.MilliCpu (cpu_nz); a pod with GPUs adds its per-GPU milli to every
+// device named in `mask`.  False (the reference skips the pod) when the CPU left would exceed the
+// capacity, a named device does not exist or a device would exceed 1000 milli left.  *f_after is
+// written only on success.  frag_F is used unchanged: same per-bin order, no fused multiply-add.
+template <bool kTyped>
+KSIM_HD bool victim_eval(int cpuL, const int (&gl)[kMaxGpu], int gpu_cnt, uint32_t typebit, int cap, int cpu_nz,
+                         int milli, int num, unsigned mask, const TypDev* __restrict__ tp, int ncpu, int nt,
+                         double* f_after) {
+  const long long cpu_new = (long long)cpuL + cpu_nz;
+  if (cpu_new > (long long)cap) return false;
+  int g2[kMaxGpu];
+  bool ok = true;
+#pragma unroll
+  for (int g = 0; g < kMaxGpu; ++g) {
+    const bool named = num > 0 && ((mask >> g) & 1u);
+    const int v = gl[g] + (named ? milli : 0);
+    ok = ok && !(named && (g >= gpu_cnt || v > kMilli));
+    g2[g] = v;
+  }
+  if (num > 0 && (mask >> kMaxGpu) != 0u) ok = false;
+  if (!ok) return false;
+  *f_after = frag_F<kTyped>((int)cpu_new, g2, typebit, tp, ncpu, nt);
+  return true;
+}
+
+// What k_desched_eval leaves per event (32 B).  node < 0: not a candidate (a delete event, a pod that
+// is not bound any more, or a record that does not validate).
+struct __align__(16) EvalRec {
+  double f_node;    // F(final state of the node)
+  double f_after;   // F(node + pod), valid when ok
+  int32_t node;
+  int32_t gpu_mask;
+  int32_t ok;       // Add succeeded
+  int32_t pad;
+};
+static_assert(sizeof(EvalRec) == 32, "EvalRec layout");
+static_assert(sizeof(ksim_victim) == 40, "ksim_victim layout");
+
+constexpr int kEvalBlock = 256;
+constexpr int kSelBlock = 256;
+constexpr int kSelNodeBytes = 20;          // per-node tables of k_desched_select: key 8, rank 4, start 4, end 4
+constexpr int kSelLdsBytes = 60 * 1024;    // they sit in LDS up to this size (3072 nodes), in HBM beyond
+// one replica's tables in HBM: 16-byte aligned, so the 8-byte keys at its start are aligned for any N
+KSIM_HD size_t sel_tab_stride(int N) { return ((size_t)N * kSelNodeBytes + 15) & ~(size_t)15; }
+
+struct DsArgs {
+  const ReplicaDev* reps;
+  const long long* eoff;   // [R + 1] first event slot of each replica in the per-event buffers
+  EvalRec* eval;           // [Σ E]
+  uint8_t* gone;           // [Σ E] creation events whose delete took effect
+  int32_t* plist;          // [Σ E] k_desched_select: candidate events grouped by node
+  ksim_victim* vict;       // [Σ E]
+  int32_t* bound;          // [R] pods still bound
+  const int32_t* budget;   // [R]
+  int32_t* n_vict;         // [R]
+  uint8_t* tab;            // [R][sel_tab_stride(N)] the per-node tables when they do not fit in LDS, else null
+  int N;
+  int policy;              // ksim_desched_policy
+};
+
+// grid (ceil(E_max / kEvalBlock), R): gone[ref] = 1 for every delete event that took effect.
+__global__ __launch_bounds__(kEvalBlock) void k_desched_mark(DsArgs a) {
+  const int r = (int)blockIdx.y;
+  const ReplicaDev rp = a.reps[r];
+  const int e = (int)blockIdx.x * kEvalBlock + (int)threadIdx.x;
+  if (e >= rp.n_events) return;
+  const PodDev p = rp.ev[e];
+  if (!(p.flags & kPodDelete) || rp.res[e].status != ST_DELETED) return;
+  if (p.ref >= 0 && p.ref < e) a.gone[a.eoff[r] + p.ref] = 1;
+}
+
+// grid (ceil(E_max / kEvalBlock), R), the replica's typical table staged in LDS: the candidate record
+// of every event and the replica's bound-pod count.
+__global__ __launch_bounds__(kEvalBlock) void k_desched_eval(DsArgs a, const TypDev* __restrict__ tp_all) {
+  const int r = (int)blockIdx.y;
+  const ReplicaDev rp = a.reps[r];
+  __shared__ TypDev s_tp[kMaxTypical];
+  {
+    const TypDev* tp = tp_all + (size_t)r * kMaxTypical;
+    for (int i = (int)threadIdx.x; i < rp.nt * 2; i += kEvalBlock)
+      reinterpret_cast<uint4*>(s_tp)[i] = reinterpret_cast<const uint4*>(tp)[i];
+    __syncthreads();
+  }
+  const int e = (int)blockIdx.x * kEvalBlock + (int)threadIdx.x;
+  bool bound = false;
+  if (e < rp.n_events) {
+    EvalRec out;
+    out.f_node = 0.0;
+    out.f_after = 0.0;
+    out.node = -1;
+    out.gpu_mask = 0;
+    out.ok = 0;
+    out.pad = 0;
+    const PodDev p = rp.ev[e];
+    const ResultDev res = rp.res[e];
+    bound = !(p.flags & kPodDelete) && res.status == ST_OK && !a.gone[a.eoff[r] + e];
+    // the record is validated before it indexes anything: the node, then the mask against its GPUs
+    if (bound && res.node >= 0 && res.node < a.N && res.gpu_mask >= 0) {
+      const NodeV n = load_node(rp.nodes + res.node);
+      const int cnt = n.gpu_cnt();
+      if (cnt <= kMaxGpu && ((unsigned)res.gpu_mask >> cnt) == 0u) {
+        int gl[kMaxGpu];
+        unpack_gl(n, gl);
+        const uint32_t tb = 1u << n.gpu_type();
+        const int cap = rp.cap[res.node];
+        out.node = res.node;
+        out.gpu_mask = res.gpu_mask;
+        if (rp.typed) {
+          out.f_node = frag_F<true>(n.cpu_left, gl, tb, s_tp, rp.ncpu, rp.nt);
+          out.ok = victim_eval<true>(n.cpu_left, gl, cnt, tb, cap, p.cpu_nz, p.milli, p.num, (unsigned)res.gpu_mask,
+                                     s_tp, rp.ncpu, rp.nt, &out.f_after) ? 1 : 0;
+        } else {
+          out.f_node = frag_F<false>(n.cpu_left, gl, tb, s_tp, rp.ncpu, rp.nt);
+          out.ok = victim_eval<false>(n.cpu_left, gl, cnt, tb, cap, p.cpu_nz, p.milli, p.num, (unsigned)res.gpu_mask,
+                                      s_tp, rp.ncpu, rp.nt, &out.f_after) ? 1 : 0;
+        }
+      }
+    }
+    a.eval[a.eoff[r] + e] = out;
+  }
+  // the pods in the API: every bound pod, candidate or not (deschedule.go:21, :27)
+  const unsigned long long m = __ballot(bound);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(a.bound + r, (int)__popcll(m));
+}
+
+// int64(frag_before - frag_after): fp64 subtraction, truncation toward zero (deschedule_utils.go:92).
+// Both are sums of at most 256 terms freq x milli <= 8000, so the difference is far inside int64.
+KSIM_HD long long victim_score(double before, double after) { return (long long)(before - after); }
+
+// A node's queue key: the bits of its priority (a non-negative double: monotone as an integer) + 1; 0 = not queued.
+KSIM_HD unsigned long long prio_key(double f) { return __builtin_bit_cast(unsigned long long, f) + 1ull; }
+KSIM_HD double key_prio(unsigned long long k) { return __builtin_bit_cast(double, k - 1ull); }
+
+struct NodePick {
+  unsigned long long key;
+  unsigned rank;
+  int idx;
+};
+// (priority desc, name rank asc)
+__device__ __forceinline__ bool better(const NodePick& x, const NodePick& y) {
+  return x.key > y.key || (x.key == y.key && x.key != 0ull && x.rank < y.rank);
+}
+__device__ __forceinline__ NodePick wave_best(NodePick v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    NodePick w;
+    w.key = __shfl_xor(v.key, o, 64);
+    w.rank = __shfl_xor(v.rank, o, 64);
+    w.idx = __shfl_xor(v.idx, o, 64);
+    if (better(w, v)) v = w;
+  }
+  return v;
+}
+
+// One workgroup per replica.  Setup: the candidates that can ever be a victim (Add succeeded and the score
+// against the node's own F is positive: a node's priority only falls, so a score that is not positive now never
+// will be) grouped by node -- count, block scan, fill -- and every node with such a candidate queued at F(node).
+// Loop, at most once per queued node plus once per unit of budget: pop the node of the highest priority, pick
+// its pod of the highest score (ties: the lowest event), emit it and re-key the node with F(node + pod)
+// (fragMultiPod) or drop it (fragOnePod: one visit per node); a node without a victim is dropped.
+__global__ __launch_bounds__(kSelBlock) void k_desched_select(DsArgs a) {
+  extern __shared__ __align__(16) uint8_t s_dyn[];
+  __shared__ NodePick s_pick[kSelBlock / 64];
+  __shared__ unsigned long long s_pod[kSelBlock / 64];
+  __shared__ int s_pj[kSelBlock / 64];
+  __shared__ int s_scan[kSelBlock / 64];
+  const int r = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const ReplicaDev rp = a.reps[r];
+  const int N = a.N, E = rp.n_events;
+  const EvalRec* ev = a.eval + a.eoff[r];
+  int32_t* plist = a.plist + a.eoff[r];
+  ksim_victim* vict = a.vict + a.eoff[r];
+  uint8_t* base = a.tab ? a.tab + (size_t)r * sel_tab_stride(N) : s_dyn;
+  unsigned long long* nkey = reinterpret_cast<unsigned long long*>(base);
+  unsigned* nrank = reinterpret_cast<unsigned*>(base + (size_t)N * 8);
+  int* nstart = reinterpret_cast<int*>(base + (size_t)N * 12);
+  int* nend = reinterpret_cast<int*>(base + (size_t)N * 16);
+
+  for (int i = tid; i < N; i += kSelBlock) {
+    nkey[i] = 0ull;
+    nrank[i] = rp.nodes[i].name_rank;
+    nend[i] = 0;
+  }
+  __syncthreads();
+  for (int e = tid; e < E; e += kSelBlock) {
+    const EvalRec c = ev[e];
+    if (c.node >= 0 && c.ok && victim_score(c.f_node, c.f_after) > 0) {
+      atomicAdd(&nend[c.node], 1);
+      nkey[c.node] = prio_key(c.f_node);  // (every candidate of a node stores the same value)
+    }
+  }
+  __syncthreads();
+  {  // exclusive scan of the counts: a contiguous chunk per thread, the wave sums by shuffles, the waves through LDS
+    const int per = (N + kSelBlock - 1) / kSelBlock;
+    const int lo = min(N, tid * per), hi = min(N, lo + per);
+    int sum = 0;
+    for (int i = lo; i < hi; ++i) sum += nend[i];
+    int incl = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int x = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += x;
+    }
+    if (lane == 63) s_scan[w] = incl;
+    __syncthreads();
+    int run = incl - sum;
+    for (int i = 0; i < w; ++i) run += s_scan[i];
+    for (int i = lo; i < hi; ++i) {
+      const int c = nend[i];
+      nstart[i] = run;
+      nend[i] = run;
+      run += c;
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < E; e += kSelBlock) {
+    const EvalRec c = ev[e];
+    if (c.node >= 0 && c.ok && victim_score(c.f_node, c.f_after) > 0) plist[atomicAdd(&nend[c.node], 1)] = e;
+  }
+  __syncthreads();
+
+  int left = a.budget[r], nv = 0;
+  for (int it = 0; left > 0 && it < N + a.budget[r]; ++it) {
+    NodePick best;
+    best.key = 0ull;
+    best.rank = 0u;
+    best.idx = -1;
+    for (int i = tid; i < N; i += kSelBlock) {
+      NodePick c;
+      c.key = nkey[i];
+      c.rank = nrank[i];
+      c.idx = i;
+      if (better(c, best)) best = c;
+    }
+    best = wave_best(best);
+    if (lane == 0) s_pick[w] = best;
+    __syncthreads();
+    best = s_pick[0];
+#pragma unroll
+    for (int i = 1; i < kSelBlock / 64; ++i)
+      if (better(s_pick[i], best)) best = s_pick[i];
+    if (best.key == 0ull) break;  // the queue is empty (uniform: every thread read the same s_pick)
+    const double prio = key_prio(best.key);
+    // the node's pod of the highest score: key = score << 32 | ~event (score < 2^22: the bound above)
+    unsigned long long pk = 0ull;
+    int pj = -1;
+    for (int j = nstart[best.idx] + tid; j < nend[best.idx]; j += kSelBlock) {
+      const int e = plist[j];
+      if (e < 0) continue;  // evicted on an earlier pop
+      const long long s = victim_score(prio, ev[e].f_after);
+      if (s <= 0) continue;
+      const unsigned long long k = ((unsigned long long)s << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)e);
+      if (k > pk) {
+        pk = k;
+        pj = j;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long k2 = __shfl_xor(pk, o, 64);
+      const int j2 = __shfl_xor(pj, o, 64);
+      if (k2 > pk) {
+        pk = k2;
+        pj = j2;
+      }
+    }
+    if (lane == 0) {
+      s_pod[w] = pk;
+      s_pj[w] = pj;
+    }
+    __syncthreads();
+    pk = s_pod[0];
+    pj = s_pj[0];
+#pragma unroll
+    for (int i = 1; i < kSelBlock / 64; ++i)
+      if (s_pod[i] > pk) {
+        pk = s_pod[i];
+        pj = s_pj[i];
+      }
+    if (pk != 0ull) {
+      if (tid == 0) {
+        const int e = plist[pj];
+        const EvalRec c = ev[e];
+        ksim_victim v;
+        v.event = e;
+        v.node = c.node;
+        v.gpu_mask = c.gpu_mask;
+        v.reserved = 0;
+        v.score = (long long)(pk >> 32);
+        v.frag_before = prio;
+        v.frag_after = c.f_after;
+        vict[nv] = v;
+        plist[pj] = -1;
+        nkey[best.idx] = a.policy == KSIM_DESCHED_FRAG_MULTI_POD ? prio_key(c.f_after) : 0ull;
+      }
+      ++nv;
+      --left;
+    } else if (tid == 0) {
+      nkey[best.idx] = 0ull;
+    }
+    __syncthreads();  // the re-key and the eviction mark before the next pop; s_pick / s_pod free again
+  }
+  if (tid == 0) a.n_vict[r] = nv;
+}
+
+}  // namespace ksim_ds

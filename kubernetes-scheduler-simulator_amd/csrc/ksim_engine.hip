@@ -698,6 +698,7 @@ struct GranV {
 // step loop, as k_memo's does.
 #include "ksim_random_go.hpp"
 #include "ksim_scan1.hpp"
+#include "ksim_desched.hpp"
 
 template <int kPol, int kSub, bool kGeneral>
 __global__ __launch_bounds__(ksim_replay::kRBlock, (kSub == 0 && kPol >= POL_BESTFIT && kPol <= POL_RANDOM &&
@@ -1941,6 +1942,21 @@ struct ksim_engine {
   std::vector<std::vector<unsigned long long>> go_state;
   DevBuf<unsigned long long> d_go;
   int64_t last_steps = 0;
+  // descheduling plan (ksim_engine_deschedule): made from the results and final node records of the last
+  // completed run; per-event buffers at each replica's offset ds_eoff[r]
+  bool ran = false;      // a ksim_engine_run completed since the last set_nodes / set_typical / load_events
+  bool ds_done = false;  // a plan of that run is held
+  DevBuf<ksim_ds::EvalRec> d_ds_eval;
+  DevBuf<uint8_t> d_ds_gone;
+  DevBuf<int32_t> d_ds_plist;
+  DevBuf<ksim_victim> d_ds_vict;
+  DevBuf<int32_t> d_ds_cnt;    // [3][R] bound pods, budget, victims
+  DevBuf<long long> d_ds_eoff;
+  DevBuf<uint8_t> d_ds_tab;    // k_desched_select's per-node tables when they do not fit in LDS
+  std::vector<long long> ds_eoff;
+  std::vector<int32_t> ds_budget, ds_nv;
+  hipEvent_t ev_ds0 = nullptr, ev_ds1 = nullptr;
+  double last_ds_ms = 0;
 };
 
 static int check_gfx950(int dev) {
@@ -3068,7 +3084,10 @@ void ksim_engine_destroy(ksim_engine* e) {
               e->d_cpum, e->d_pws, e->d_m_evcls, e->d_topg, e->d_m_hkeys, e->d_m_wgmap, e->d_h_cg, e->d_h_cls,
               e->d_h_cgrp, e->d_h_gpod, e->d_h_evc, e->d_h_st, e->d_h_ns, e->d_h_nstate, e->d_h_gsc, e->d_h_mtoff,
               e->d_h_mtab, e->d_h_na, e->d_h_keys, e->d_h_l1, e->d_h_l2, e->d_h_cnt, e->d_h_prof, e->d_h_hist,
-              e->d_go, e->d_ggran, e->d_hgargs, e->d_rgran, e->d_rgreps, e->d_rglist, e->d_done, e->d_ragg);
+              e->d_go, e->d_ggran, e->d_hgargs, e->d_rgran, e->d_rgreps, e->d_rglist, e->d_done, e->d_ragg,
+              e->d_ds_eval, e->d_ds_gone, e->d_ds_plist, e->d_ds_vict, e->d_ds_cnt, e->d_ds_eoff, e->d_ds_tab);
+  if (e->ev_ds0) (void)hipEventDestroy(e->ev_ds0);
+  if (e->ev_ds1) (void)hipEventDestroy(e->ev_ds1);
   for (int i = 0; i < ksim_engine::kSide; ++i) {
     if (e->side[i]) (void)hipStreamDestroy(e->side[i]);
     if (e->side_ev[i]) (void)hipEventDestroy(e->side_ev[i]);
@@ -3164,6 +3183,7 @@ int ksim_engine_set_nodes(ksim_engine* e, int replica, const ksim_node* nodes) {
   e->h_nodes[replica].assign(nodes, nodes + e->N);
   e->h_rec[replica] = h;
   e->mplan_dirty = true;  // k_hmemo's plan holds the distinct initial node states
+  e->ran = e->ds_done = false;
   e->total_gpus[replica] = gpus;
   KSIM_HIP(hipSetDevice(e->device));
   KSIM_HIP(hipMemcpyAsync(e->d_cap + (size_t)replica * e->N, cap.data(), sizeof(int32_t) * e->N, hipMemcpyHostToDevice,
@@ -3217,6 +3237,7 @@ int ksim_engine_set_typical(ksim_engine* e, int replica, const ksim_typical* tp,
   e->reps[replica].typed = typed ? 1 : 0;
   e->h_tp[replica] = h;
   e->mplan_dirty = true;  // k_hmemo's plan holds per-model views of the table
+  e->ran = e->ds_done = false;
   int rc = upload_reps(e);
   if (rc) return rc;
   KSIM_HIP(hipStreamSynchronize(e->stream));
@@ -3451,6 +3472,7 @@ int ksim_engine_bind(ksim_engine* e, int replica, const ksim_pod* pod, int node,
 int ksim_engine_load_events(ksim_engine* e, int replica, const ksim_pod* events, int n) {
   if (e) e->mplan_dirty = true;
   if (!e || replica < 0 || replica >= e->R || n < 0 || (n > 0 && !events)) return KSIM_EINVAL;
+  e->ran = e->ds_done = false;
   std::vector<PodDev> h(n);
   std::vector<char> gone(std::max(n, 1), 0);  // creations already deleted (the reference deletes a pod once)
   for (int i = 0; i < n; ++i) {
@@ -4359,6 +4381,7 @@ int ksim_engine_run(ksim_engine* e) {
   KSIM_HIP(hipSetDevice(e->device));
   const RunEnv env = read_env();
   e->report_done = false;
+  e->ran = e->ds_done = false;
   e->grp_rev_used = 0;
   e->tev_used = 0u;  // KSIM_GROUP_TIMES: only run_persistent's concurrent groups record side-stream ends
   e->last_launches = 0;
@@ -4428,6 +4451,7 @@ int ksim_engine_run(ksim_engine* e) {
     if (fail & 64) std::fprintf(stderr, "ksim: the overlapped report waited too long for a replay (fail bits 0x%x)\n", fail);
     if (fail) return KSIM_ESTATE;  // a granule poll or an LDS wait timed out
   }
+  e->ran = true;
   return KSIM_OK;
 }
 
@@ -5099,6 +5123,104 @@ int ksim_engine_get_nodes(ksim_engine* e, int replica, ksim_node* out) {
     for (int g = 0; g < kMaxGpu; ++g) o.gpu_used_milli[g] = g < n.gpu_cnt ? kMilli - (int)n.gl[g] : 0;
     for (int k = 0; k < kNumTags; ++k) o.tag_count[k] = tags[(size_t)i * kTagStride + k];
   }
+  return KSIM_OK;
+}
+
+// The descheduling plan of every replica from the last run's results and final node records
+// (ksim_desched.hpp): mark, evaluate, the budgets on the host from the bound-pod counts, select.
+int ksim_engine_deschedule(ksim_engine* e, int policy, double ratio) {
+  if (check_gfx950(e ? e->device : 0)) return KSIM_ENODEV;
+  if (!e) return KSIM_EINVAL;
+  if (policy != KSIM_DESCHED_FRAG_ONE_POD && policy != KSIM_DESCHED_FRAG_MULTI_POD) return KSIM_EINVAL;
+  if (!(ratio >= 0.0)) return KSIM_EINVAL;  // negative or NaN
+  if (e->shard_world > 0) return KSIM_ENOTSUP;
+  if (!e->ran) return KSIM_ESTATE;
+  e->ds_done = false;
+  KSIM_HIP(hipSetDevice(e->device));
+  const int R = e->R;
+  int max_ev = 0;
+  e->ds_eoff.assign((size_t)R + 1, 0);
+  for (int r = 0; r < R; ++r) {
+    e->ds_eoff[r + 1] = e->ds_eoff[r] + e->n_events[r];
+    max_ev = std::max(max_ev, e->n_events[r]);
+  }
+  const size_t tot = (size_t)e->ds_eoff[R];
+  int rc = e->d_ds_eval.ensure(tot);
+  if (!rc) rc = e->d_ds_gone.ensure(tot);
+  if (!rc) rc = e->d_ds_plist.ensure(tot);
+  if (!rc) rc = e->d_ds_vict.ensure(tot);
+  if (!rc) rc = e->d_ds_cnt.ensure((size_t)3 * R);
+  if (!rc) rc = e->d_ds_eoff.upload(e->ds_eoff, e->stream);
+  const size_t tab = (size_t)e->N * ksim_ds::kSelNodeBytes;
+  const bool in_lds = tab <= (size_t)ksim_ds::kSelLdsBytes;
+  if (!rc && !in_lds) rc = e->d_ds_tab.ensure(ksim_ds::sel_tab_stride(e->N) * R);
+  if (rc) return rc;
+  if (!e->ev_ds0) KSIM_HIP(hipEventCreate(&e->ev_ds0));
+  if (!e->ev_ds1) KSIM_HIP(hipEventCreate(&e->ev_ds1));
+  ksim_ds::DsArgs a;
+  a.reps = e->d_reps;
+  a.eoff = e->d_ds_eoff.p;
+  a.eval = e->d_ds_eval.p;
+  a.gone = e->d_ds_gone.p;
+  a.plist = e->d_ds_plist.p;
+  a.vict = e->d_ds_vict.p;
+  a.bound = e->d_ds_cnt.p;
+  a.budget = e->d_ds_cnt.p + R;
+  a.n_vict = e->d_ds_cnt.p + 2 * R;
+  a.tab = in_lds ? nullptr : e->d_ds_tab.p;
+  a.N = e->N;
+  a.policy = policy;
+  KSIM_HIP(hipEventRecord(e->ev_ds0, e->stream));
+  if (tot) KSIM_HIP(hipMemsetAsync(e->d_ds_gone.p, 0, tot, e->stream));
+  KSIM_HIP(hipMemsetAsync(e->d_ds_cnt.p, 0, sizeof(int32_t) * 3 * R, e->stream));
+  if (max_ev > 0) {
+    const dim3 grid((unsigned)((max_ev + ksim_ds::kEvalBlock - 1) / ksim_ds::kEvalBlock), (unsigned)R);
+    hipLaunchKernelGGL(ksim_ds::k_desched_mark, grid, dim3(ksim_ds::kEvalBlock), 0, e->stream, a);
+    KSIM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ksim_ds::k_desched_eval, grid, dim3(ksim_ds::kEvalBlock), 0, e->stream, a, (const TypDev*)e->d_tp);
+    KSIM_HIP(hipGetLastError());
+  }
+  std::vector<int32_t> bound((size_t)R, 0);
+  KSIM_HIP(hipMemcpyAsync(bound.data(), a.bound, sizeof(int32_t) * R, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipStreamSynchronize(e->stream));
+  // deschedule.go:27 int(math.Ceil(ratio * float64(len(podMap)))); never more than the pods there are
+  e->ds_budget.assign((size_t)R, 0);
+  for (int r = 0; r < R; ++r)
+    e->ds_budget[r] = (int32_t)std::min(std::ceil(ratio * (double)bound[r]), (double)bound[r]);
+  KSIM_HIP(hipMemcpyAsync(e->d_ds_cnt.p + R, e->ds_budget.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(ksim_ds::k_desched_select, dim3((unsigned)R), dim3(ksim_ds::kSelBlock), in_lds ? tab : (size_t)0,
+                     e->stream, a);
+  KSIM_HIP(hipGetLastError());
+  e->ds_nv.assign((size_t)R, 0);
+  KSIM_HIP(hipMemcpyAsync(e->ds_nv.data(), a.n_vict, sizeof(int32_t) * R, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipEventRecord(e->ev_ds1, e->stream));
+  KSIM_HIP(hipStreamSynchronize(e->stream));
+  float ms = 0;
+  KSIM_HIP(hipEventElapsedTime(&ms, e->ev_ds0, e->ev_ds1));
+  e->last_ds_ms = ms;
+  e->ds_done = true;
+  return KSIM_OK;
+}
+
+int ksim_engine_get_victims(ksim_engine* e, int replica, ksim_victim* out, int cap, int* n_out, int* budget_out) {
+  if (!e || replica < 0 || replica >= e->R || cap < 0 || !n_out) return KSIM_EINVAL;
+  if (!e->ds_done) return KSIM_ESTATE;
+  const int n = e->ds_nv[replica];
+  *n_out = n;
+  if (budget_out) *budget_out = e->ds_budget[replica];
+  if (cap < n) return KSIM_ERANGE;
+  if (n == 0) return KSIM_OK;
+  if (!out) return KSIM_EINVAL;
+  KSIM_HIP(hipSetDevice(e->device));
+  KSIM_HIP(hipMemcpyAsync(out, e->d_ds_vict.p + e->ds_eoff[replica], sizeof(ksim_victim) * n, hipMemcpyDeviceToHost,
+                          e->stream));
+  KSIM_HIP(hipStreamSynchronize(e->stream));
+  return KSIM_OK;
+}
+
+int ksim_engine_last_deschedule_ms(ksim_engine* e, double* ms) {
+  if (!e || !ms) return KSIM_EINVAL;
+  *ms = e->last_ds_ms;
   return KSIM_OK;
 }
 

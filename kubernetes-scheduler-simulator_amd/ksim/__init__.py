@@ -128,8 +128,17 @@ class ReplayCfg(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("tune_ratio", C.c_double), ("shuffle", C.c_int32), ("informer_draws", C.c_int32)]
 
 
+class Victim(C.Structure):
+    """ksim_victim: one pod of a descheduling plan (Engine.deschedule / Engine.victims)."""
+    _fields_ = [("event", C.c_int32), ("node", C.c_int32), ("gpu_mask", C.c_int32), ("reserved", C.c_int32),
+                ("score", C.c_int64), ("frag_before", C.c_double), ("frag_after", C.c_double)]
+
+
+# deschedule.go:14-17 descheduleConfig.policy
+DESCHED_POLICY = {"fragOnePod": 0, "fragMultiPod": 1}
+
 assert C.sizeof(Node) == 128 and C.sizeof(Pod) == 48 and C.sizeof(Typical) == 32 and C.sizeof(Result) == 24
-assert C.sizeof(Report) == 112 and C.sizeof(PowerReport) == 32
+assert C.sizeof(Report) == 112 and C.sizeof(PowerReport) == 32 and C.sizeof(Victim) == 40
 
 _LIB = None
 
@@ -195,6 +204,9 @@ SIGNATURES = {
     "ksim_go_rand": (C.c_int, [C.c_int64, C.c_int, C.c_int64, C.c_int, _P(C.c_int64)]),
     "ksim_trace_replay_go_state": (C.c_int, [_VP, _P(ReplayCfg), _P(C.c_uint64), _P(C.c_int32), _P(C.c_int64)]),
     "ksim_engine_set_go_stream": (C.c_int, [_VP, C.c_int, _P(C.c_uint64), C.c_int, C.c_int]),
+    "ksim_engine_deschedule": (C.c_int, [_VP, C.c_int, C.c_double]),
+    "ksim_engine_get_victims": (C.c_int, [_VP, C.c_int, _P(Victim), C.c_int, _P(C.c_int), _P(C.c_int)]),
+    "ksim_engine_last_deschedule_ms": (C.c_int, [_VP, _P(C.c_double)]),
 }
 
 
@@ -721,6 +733,30 @@ class Engine:
         out = (Node * self.N)()
         check(lib().ksim_engine_get_nodes(self.h, r, out), "get_nodes")
         return out
+
+    # fragmentation-aware descheduling (deschedule.go:20-47); ksim.desched runs the rescheduling
+    def deschedule(self, policy, ratio):
+        """Plan, for every replica, the pods to evict after the last run(): policy "fragOnePod" /
+        "fragMultiPod" (or the ksim_desched_policy number), budget ceil(ratio * bound pods).  Changes no
+        cluster state; returns the plan's device time in ms."""
+        pol = DESCHED_POLICY[policy] if isinstance(policy, str) else int(policy)
+        check(lib().ksim_engine_deschedule(self.h, pol, float(ratio)), "deschedule")
+        return self.last_deschedule_ms()
+
+    def victims(self, r):
+        """(victims of replica r in eviction order, budget): a list of Victim and an int."""
+        n, budget = C.c_int(0), C.c_int(0)
+        rc = lib().ksim_engine_get_victims(self.h, r, None, 0, C.byref(n), C.byref(budget))
+        if rc != KSIM_ERANGE:
+            check(rc, "get_victims")
+        out = (Victim * max(1, n.value))()
+        check(lib().ksim_engine_get_victims(self.h, r, out, n.value, C.byref(n), C.byref(budget)), "get_victims")
+        return [out[i] for i in range(n.value)], budget.value
+
+    def last_deschedule_ms(self):
+        ms = C.c_double(0)
+        check(lib().ksim_engine_last_deschedule_ms(self.h, C.byref(ms)), "last_deschedule_ms")
+        return ms.value
 
 
 SHARD_ID_BYTES = 128
