@@ -40,6 +40,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <vector>
 #include <chrono>
 #include <thread>
@@ -1778,40 +1779,49 @@ __global__ __launch_bounds__(64) void k_reserve(ReplicaDev* reps, const TypDev* 
 // ---------------------------------------------------------------------------
 // Host engine object
 // ---------------------------------------------------------------------------
+struct MemoPlan;
+struct HPlan;
+// Every device resource is a member handle (ksim_host.hpp) that frees itself: a new buffer is one new member and nothing
+// else.  Declaration order carries meaning, since members go in reverse: the streams come first and so go last, after
+// every buffer and event used on them.  Before that the destructor sets the device, drains the side streams and then
+// the engine's (no dispatch, or a profiler's completion callback on it, may outlive its buffers, streams or graph),
+// destroys the graph and the communicator, and closes the peers' IPC-opened buffers.
 struct ksim_engine {
   int device = 0;
+  static constexpr int kSide = kSideStreams;
+  DevStream stream;
+  DevStream side[kSide];  // for concurrent single-workgroup k_replay groups (created on first use)
   int N = 0, R = 0, NB = 64, bpr = 0, K = 256;
   int run_mode = 0;        // 0: auto (k_memo for FGD when it fits, else k_replay), 1: k_step per pod (hipGraph),
                            // 2: k_replay only, 3: k_memo required for FGD
   int wgs_req = 0;         // requested workgroups per replica (0 = auto)
   int cus = 256;
   bool coop = true;  // K > 1 persistent grids through hipLaunchCooperativeKernel (KSIM_COOP=0: plain launch)
-  unsigned long long* d_gran = nullptr;
+  DevBuf<unsigned long long> d_gran;
   DevBuf<int2> d_hist;
-  int* d_fail = nullptr;
-  int* d_replist = nullptr;              // replicas ordered by policy (k_replay groups)
+  DevBuf<int> d_fail;
+  DevBuf<int> d_replist;              // replicas ordered by policy (k_replay groups)
   DevBuf<unsigned long long> d_prof;  // KSIM_PROFILE=1: k_replay phase timers
   int last_K = 0;
-  hipStream_t stream = nullptr;
-  NodeRec* d_nodes = nullptr;
-  NodeRec* d_nodes_init = nullptr;  // cluster state given to set_nodes (run() restarts from it)
-  uint16_t* d_tags = nullptr;  // per replica: N*16 u16 tags, then N int rank->index
-  uint16_t* d_tags_init = nullptr;
+  DevBuf<NodeRec> d_nodes;
+  DevBuf<NodeRec> d_nodes_init;  // cluster state given to set_nodes (run() restarts from it)
+  DevBuf<uint16_t> d_tags;  // per replica: N*16 u16 tags, then N int rank->index
+  DevBuf<uint16_t> d_tags_init;
   size_t tags_stride = 0;      // u16 elements per replica
-  TypDev* d_tp = nullptr;
-  Accum* d_acc = nullptr;
-  ReplicaDev* d_reps = nullptr;
-  int* d_base = nullptr;
-  int* d_scratch = nullptr;     // single-pod calls: [0] mask
-  PodDev* d_pod = nullptr;      // single-pod calls
-  ResultDev* d_res1 = nullptr;  // single-pod calls
-  uint8_t* d_feas = nullptr;
-  int32_t* d_score = nullptr;
-  int32_t* d_gpu = nullptr;
+  DevBuf<TypDev> d_tp;
+  DevBuf<Accum> d_acc;
+  DevBuf<ReplicaDev> d_reps;
+  DevBuf<int> d_base;
+  DevBuf<int> d_scratch;     // single-pod calls: [0] mask
+  DevBuf<PodDev> d_pod;      // single-pod calls
+  DevBuf<ResultDev> d_res1;  // single-pod calls
+  DevBuf<uint8_t> d_feas;
+  DevBuf<int32_t> d_score;
+  DevBuf<int32_t> d_gpu;
   std::vector<ReplicaDev> reps;
   std::vector<std::vector<ksim_node>> h_nodes;  // caller's static node fields per replica
-  std::vector<PodDev*> d_ev;
-  std::vector<ResultDev*> d_res;
+  std::vector<DevBuf<PodDev>> d_ev;
+  std::vector<DevBuf<ResultDev>> d_res;
   std::vector<int> n_events;
   std::vector<char> has_delete;  // the replica's stream has deletion events (k_replay keeps a bind history)
   // k_memo (memoised FGD replay): per replica the distinct pod requests of its creation events
@@ -1834,9 +1844,9 @@ struct ksim_engine {
   DevBuf<unsigned long long> d_done;  // [2 + R] the overlapped report's queue (ksim_scan1.hpp Scan1Args::done)
   DevBuf<__int128> d_ragg;     // [R][kScanPartsMax][2][kFields] the multi-workgroup report scan's part sums
   unsigned done_epoch = 0;
-  hipEvent_t ev_ovl = nullptr;    // the queue's tickets zeroed (the report's stream waits on it)
-  double* d_th = nullptr;       // FGD score steps (build_score_thresholds), null if unusable
-  struct MemoPlan* mplan = nullptr;  // the FGD replicas' k_memo plan, uploaded before the timed run
+  DevEvent ev_ovl;    // the queue's tickets zeroed (the report's stream waits on it)
+  DevBuf<double> d_th;       // FGD score steps (build_score_thresholds), null if unusable
+  std::unique_ptr<MemoPlan> mplan;  // the FGD replicas' k_memo plan, uploaded before the timed run
   bool mplan_dirty = true;           // events or policies changed since the plan was made
   bool mplan_ok = false;
   std::vector<int> mplan_all;   // the FGD replicas the plans were made for (cache key)
@@ -1847,7 +1857,7 @@ struct ksim_engine {
   int mplan_max_ev = -1;
   int last_memo = 0;
   // k_hmemo (memoised FGD replay, keys in HBM): the plan and its device tables
-  struct HPlan* hplan = nullptr;
+  std::unique_ptr<HPlan> hplan;
   bool hplan_ok = false;
   DevBuf<int> d_h_cg;
   DevBuf<PodDev> d_h_cls;
@@ -1871,69 +1881,65 @@ struct ksim_engine {
   int last_rgo = 0;  // replicas the last run replayed on k_random_go
   int last_scan1 = 0;  // replicas the last run replayed on k_scan1
   int last_launches = 0, last_streams = 0;  // replay launches of the last run, side streams they ran on (0: none)
-  std::vector<hipEvent_t> grp_rev;  // concurrent groups' report kernels: a timing event pair per group
+  std::vector<DevEvent> grp_rev;  // concurrent groups' report kernels: a timing event pair per group
   int grp_rev_used = 0;             // pairs recorded by the last run
   int scan1 = 2;       // single-workgroup cheap-policy groups on k_scan1, node records in VGPRs where they fit
                        // (KSIM_VARIANT scan1=1: records in LDS; 0: k_replay)
   std::vector<std::vector<NodeRec>> h_rec;  // the records set_nodes gave each replica (k_hmemo's initial states)
   bool last_step_path = false;  // the last run went through k_step (run_mode 1 or a PWR replica)
   std::vector<int> nt;
-  hipGraphExec_t graph = nullptr;
+  GraphExec graph;
   int graph_R = -1;
   bool graph_pwr = false;    // the graph carries k_step_pwr after every k_step
-  PowerDev* d_pw = nullptr;  // [R] PWR energy model
-  uint8_t* d_cpum = nullptr; // [R][N] CPU model id per node
-  int2* d_pws = nullptr;     // [R][N] PWR phase-A scratch
+  DevBuf<PowerDev> d_pw;  // [R] PWR energy model
+  DevBuf<uint8_t> d_cpum; // [R][N] CPU model id per node
+  DevBuf<int2> d_pws;     // [R][N] PWR phase-A scratch
   std::vector<char> pw_set;  // set_power_model called
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_mid = nullptr;
-  // side streams for concurrent single-workgroup k_replay groups (created on first use)
-  static constexpr int kSide = kSideStreams;
-  hipStream_t side[kSide] = {};
-  int* h_started = nullptr;   // residency gate: host-mapped flags, one per FGD workgroup (hipHostMalloc)
-  int* d_started = nullptr;   // its device address
-  int started_cap = 0, gate_epoch = 0;
+  DevEvent ev0, ev1, ev_mid;
+  MappedFlags started;  // residency gate: host-mapped flags, one per FGD workgroup
+  int gate_epoch = 0;
   int last_ovl = 0;           // replicas the last run's overlapped report took (k_report_overlap)
   int last_gate = 0;          // the last run's residency gate: 0 none, 1 opened, -1 given up at its bound (stderr note)
   long long gate_timeouts = 0;  // gates given up at their bound, over the engine's life
   std::string last_kernels;    // the replay kernels the last run launched, '+'-joined in launch order
-  hipEvent_t side_ev[kSide] = {};
-  hipEvent_t ev_fork = nullptr;
+  DevEvent side_ev[kSide];
+  DevEvent ev_fork;
   bool report_done = false;
   // KSIM_GROUP_TIMES=1: timing events at the fork and at each used side stream's end (the last run's
   // concurrent groups, printed on stderr after the run)
-  hipEvent_t tev_fork = nullptr;
-  hipEvent_t tev_side[kSide] = {};
+  DevEvent tev_fork;
+  DevEvent tev_side[kSide];
   unsigned tev_used = 0u;
   int last_pf_memo = 0;      // PWR+FGD memo class stride of the last k_replay<PWR+FGD> launch (0: none)
   double last_ms = 0, last_report_ms = 0;
   // cluster report (ksim_engine_set_report)
   bool report = false;
-  int32_t* d_cap = nullptr;   // [R][N] allocatable milli-CPU
-  int32_t* d_mcap = nullptr;  // [R][N] allocatable memory, MiB (Unreserve's removePod guard)
-  int32_t* d_last = nullptr;  // [R][N] k_step: last event that changed each node
-  std::vector<NodeRec*> d_snap;
-  std::vector<int32_t*> d_prev;
-  std::vector<RepAcc*> d_rep;
+  DevBuf<int32_t> d_cap;   // [R][N] allocatable milli-CPU
+  DevBuf<int32_t> d_mcap;  // [R][N] allocatable memory, MiB (Unreserve's removePod guard)
+  DevBuf<int32_t> d_last;  // [R][N] k_step: last event that changed each node
+  std::vector<DevBuf<NodeRec>> d_snap;
+  std::vector<DevBuf<int32_t>> d_prev;
+  std::vector<DevBuf<RepAcc>> d_rep;
   std::vector<int64_t> total_gpus;
   // node-sharded cluster (ksim_engine_set_shard)
   int shard_world = 0;        // 0: not sharded
-  unsigned long long* d_ggran = nullptr;  // a node-sharded group's exchange granules (engine 0 of the group)
-  void* d_hgargs = nullptr;               // its per-shard k_hmemo arguments
-  unsigned long long* d_rgran = nullptr;  // a node-sharded k_replay group's exchange granules (engine 0)
-  ReplicaDev* d_rgreps = nullptr;         // its shards' replicas, and their list
-  int* d_rglist = nullptr;
+  DevBuf<unsigned long long> d_ggran;  // a node-sharded group's exchange granules (engine 0 of the group)
+  DevBuf<ksim_hmemo::HMemoArgs> d_hgargs; // its per-shard k_hmemo arguments
+  DevBuf<unsigned long long> d_rgran;  // a node-sharded k_replay group's exchange granules (engine 0)
+  DevBuf<ReplicaDev> d_rgreps;         // its shards' replicas, and their list
+  DevBuf<int> d_rglist;
   // one shard per process (ksim_shard_peer_handle / ksim_engine_set_shard_peers): this shard's exchange
   // buffer (uncached device memory, exported by IPC), the peers' buffers mapped here, the run epoch
-  unsigned long long* d_pgran = nullptr;
+  DevBuf<unsigned long long> d_pgran;
   std::vector<uint8_t> pgran_handle;      // the handle ksim_shard_peer_handle returned (exports differ per call)
   std::vector<unsigned long long*> peers;
   std::vector<char> peer_opened;
   int peer_epoch = 0;
   int shard_rank = 0, node_off = 0, n_global = 0;
   ncclComm_t comm = nullptr;  // null: in-process shard group (ksim_shard_group_run) or world 1
-  unsigned long long* d_send = nullptr;  // this shard's record {best, nfeas, err, lo|hi}
-  unsigned long long* d_recv = nullptr;  // [world][4] gathered records
-  unsigned long long** d_ptrs = nullptr; // group mode: send / recv pointer tables
+  DevBuf<unsigned long long> d_send;  // this shard's record {best, nfeas, err, lo|hi}
+  DevBuf<unsigned long long> d_recv;  // [world][4] gathered records
+  DevBuf<unsigned long long*> d_ptrs; // group mode: send / recv pointer tables
   ksim_shard_exchange_fn xfn = nullptr;  // host exchange (ksim_engine_set_shard_exchange)
   void* xuser = nullptr;
   std::vector<uint64_t> h_send, h_recv;  // its staging records
@@ -1955,8 +1961,9 @@ struct ksim_engine {
   DevBuf<uint8_t> d_ds_tab;    // k_desched_select's per-node tables when they do not fit in LDS
   std::vector<long long> ds_eoff;
   std::vector<int32_t> ds_budget, ds_nv;
-  hipEvent_t ev_ds0 = nullptr, ev_ds1 = nullptr;
+  DevEvent ev_ds0, ev_ds1;
   double last_ds_ms = 0;
+  ~ksim_engine();
 };
 
 static int check_gfx950(int dev) {
@@ -1972,7 +1979,7 @@ static int alloc_report(ksim_engine* e, int r);
 static void destroy_comm(ncclComm_t c);
 
 static int upload_reps(ksim_engine* e) {
-  KSIM_HIP(hipMemcpyAsync(e->d_reps, e->reps.data(), sizeof(ReplicaDev) * e->R, hipMemcpyHostToDevice, e->stream));
+  KSIM_HIP(hipMemcpyAsync(e->d_reps.p, e->reps.data(), sizeof(ReplicaDev) * e->R, hipMemcpyHostToDevice, e->stream));
   return KSIM_OK;
 }
 
@@ -2218,6 +2225,14 @@ static const double* score_table() {
   return ok ? th : nullptr;
 }
 
+// The table on the device, uploaded on first use; d_th stays null without a table.
+static int ensure_score_table(ksim_engine* e, hipStream_t st) {
+  if (e->d_th.p || !score_table()) return KSIM_OK;
+  if (const int rc = e->d_th.alloc(102)) return rc;
+  KSIM_HIP(hipMemcpyAsync(e->d_th.p, score_table(), sizeof(double) * 102, hipMemcpyHostToDevice, st));
+  return KSIM_OK;
+}
+
 // ---- k_hmemo planning (memoised FGD replay with the keys in HBM, ksim_hmemo.hpp) ----
 struct HPlan {
   int Cmax = 1, Gmax = 1, Smax = 1, Npad = 0, nb = 0;
@@ -2396,7 +2411,7 @@ static bool hmemo_plan(const ksim_engine* e, const std::vector<int>& reps, int s
 
 static int prepare_hmemo(ksim_engine* e, const std::vector<int>& reps, int max_ev, int forceK = 0, int forceS = 0) {
   e->hplan_ok = false;
-  if (!e->hplan) e->hplan = new HPlan();
+  if (!e->hplan) e->hplan = std::make_unique<HPlan>();
   HPlan& pl = *e->hplan;
   const int stride = std::max(max_ev, 1);
   if (!hmemo_plan(e, reps, stride, pl, forceK, forceS)) return KSIM_OK;
@@ -2422,10 +2437,7 @@ static int prepare_hmemo(ksim_engine* e, const std::vector<int>& reps, int max_e
     if ((rc = e->d_h_mtab.upload(pl.mtab, st))) return rc;
     if ((rc = e->d_h_na.ensure((size_t)Rg * pl.Mslots * ksim_hmemo::kNaStride))) return rc;
   }
-  if (!e->d_th) {
-    KSIM_HIP(hipMalloc(&e->d_th, sizeof(double) * 102));
-    KSIM_HIP(hipMemcpyAsync(e->d_th, score_table(), sizeof(double) * 102, hipMemcpyHostToDevice, st));
-  }
+  if ((rc = ensure_score_table(e, st))) return rc;
   KSIM_HIP(hipStreamSynchronize(st));  // the host vectors are pageable
   e->hplan_ok = true;
   return KSIM_OK;
@@ -2454,7 +2466,7 @@ static int prepare_memo(ksim_engine* e, int max_ev) {
   e->hplan_reps.clear();
   if (reps.empty()) return KSIM_OK;
   if (e->run_mode == 5) return prepare_hmemo(e, reps, max_ev);  // k_hmemo required
-  if (!e->mplan) e->mplan = new MemoPlan();
+  if (!e->mplan) e->mplan = std::make_unique<MemoPlan>();
   MemoPlan& pl = *e->mplan;
   // run_mode 4 (or KSIM_VARIANT=memo_decider=1 with run_mode 0): the decider variant of k_memo
   pl.decider = e->run_mode == 4 || (e->run_mode == 0 && variant("memo_decider", 0) == 1);
@@ -2491,15 +2503,8 @@ static int upload_memo(ksim_engine* e, const std::vector<int>& reps, int max_ev)
   MemoPlan& pl = *e->mplan;
   const int Rg = (int)reps.size();
   int rc;
-  if ((rc = e->d_m_pod.ensure(pl.pod.size()))) return rc;
-  if ((rc = e->d_m_owner.ensure(pl.owner.size()))) return rc;
-  if ((rc = e->d_m_wgcls.ensure(pl.wgcls.size()))) return rc;
-  if ((rc = e->d_m_wgref.ensure(pl.wgref.size()))) return rc;
-  if ((rc = e->d_m_wggrp.ensure(pl.wggrp.size()))) return rc;
   const int stride = std::max(max_ev, 1);
   if ((rc = e->d_win.ensure((size_t)Rg * stride))) return rc;
-  if ((rc = e->d_m_evo.ensure((size_t)Rg * stride))) return rc;
-  if ((rc = e->d_m_evcls.ensure((size_t)Rg * stride))) return rc;
   if ((rc = e->d_topg.ensure((size_t)Rg * stride * ksim_memo::kTopWords))) return rc;
   std::vector<int> evcls((size_t)Rg * stride, -1);
   for (int gi = 0; gi < Rg; ++gi) {
@@ -2519,23 +2524,18 @@ static int upload_memo(ksim_engine* e, const std::vector<int>& reps, int max_ev)
     }
   }
   hipStream_t st = e->stream;
-  KSIM_HIP(hipMemcpyAsync(e->d_m_evo.p, evo.data(), sizeof(int) * evo.size(), hipMemcpyHostToDevice, st));
-  KSIM_HIP(hipMemcpyAsync(e->d_m_evcls.p, evcls.data(), sizeof(int) * evcls.size(), hipMemcpyHostToDevice, st));
-  KSIM_HIP(hipMemcpyAsync(e->d_m_pod.p, pl.pod.data(), sizeof(PodDev) * pl.pod.size(), hipMemcpyHostToDevice, st));
-  KSIM_HIP(hipMemcpyAsync(e->d_m_owner.p, pl.owner.data(), sizeof(int) * pl.owner.size(), hipMemcpyHostToDevice, st));
-  KSIM_HIP(hipMemcpyAsync(e->d_m_wgcls.p, pl.wgcls.data(), sizeof(int) * pl.wgcls.size(), hipMemcpyHostToDevice, st));
-  KSIM_HIP(hipMemcpyAsync(e->d_m_wgref.p, pl.wgref.data(), sizeof(int) * pl.wgref.size(), hipMemcpyHostToDevice, st));
-  KSIM_HIP(hipMemcpyAsync(e->d_m_wggrp.p, pl.wggrp.data(), sizeof(unsigned long long) * pl.wggrp.size(),
-                          hipMemcpyHostToDevice, st));
-  if (!e->d_th && score_table()) {
-    KSIM_HIP(hipMalloc(&e->d_th, sizeof(double) * 102));
-    KSIM_HIP(hipMemcpyAsync(e->d_th, score_table(), sizeof(double) * 102, hipMemcpyHostToDevice, st));
-  }
+  if ((rc = e->d_m_evo.upload(evo, st))) return rc;
+  if ((rc = e->d_m_evcls.upload(evcls, st))) return rc;
+  if ((rc = e->d_m_pod.upload(pl.pod, st))) return rc;
+  if ((rc = e->d_m_owner.upload(pl.owner, st))) return rc;
+  if ((rc = e->d_m_wgcls.upload(pl.wgcls, st))) return rc;
+  if ((rc = e->d_m_wgref.upload(pl.wgref, st))) return rc;
+  if ((rc = e->d_m_wggrp.upload(pl.wggrp, st))) return rc;
+  if ((rc = ensure_score_table(e, st))) return rc;
   std::vector<int> wgmap((size_t)pl.nwg);
   for (int gi = 0; gi < Rg; ++gi)
     for (int w = 0; w < pl.Kr[gi]; ++w) wgmap[(size_t)pl.wgoff[gi] + w] = (gi << 8) | w;
-  if ((rc = e->d_m_wgmap.ensure(wgmap.size()))) return rc;
-  KSIM_HIP(hipMemcpyAsync(e->d_m_wgmap.p, wgmap.data(), sizeof(int) * wgmap.size(), hipMemcpyHostToDevice, st));
+  if ((rc = e->d_m_wgmap.upload(wgmap, st))) return rc;
   KSIM_HIP(hipStreamSynchronize(st));  // the host vectors are pageable and short-lived
   if (pl.hkeys && (rc = e->d_m_hkeys.ensure((size_t)pl.nwg * pl.Cw * e->N))) return rc;
   e->mplan_reps = reps;
@@ -2554,8 +2554,8 @@ static int launch_memo(ksim_engine* e, const RunEnv& env, const MemoPlan& pl, in
   if (pl.decider)
     KSIM_HIP(hipMemsetAsync(e->d_topg.p, 0, sizeof(unsigned) * (size_t)Rg * stride * ksim_memo::kTopWords, st));
   ksim_memo::MemoArgs ma;
-  ma.reps = e->d_reps;
-  ma.rep_list = e->d_replist + first;
+  ma.reps = e->d_reps.p;
+  ma.rep_list = e->d_replist.p + first;
   ma.wg_map = e->d_m_wgmap.p;
   ma.N = e->N;
   ma.K = pl.K;
@@ -2568,10 +2568,10 @@ static int launch_memo(ksim_engine* e, const RunEnv& env, const MemoPlan& pl, in
   ma.wg_ref = e->d_m_wgref.p;
   ma.wg_grp = e->d_m_wggrp.p;
   ma.ev_owner = e->d_m_evo.p;
-  ma.th = e->d_th;
+  ma.th = e->d_th.p;
   ma.win = e->d_win.p;
   ma.win_stride = stride;
-  ma.fail = e->d_fail;
+  ma.fail = e->d_fail.p;
   ma.prof = nullptr;
   ma.trace = nullptr;
   ma.trace_steps = 0;
@@ -2585,13 +2585,13 @@ static int launch_memo(ksim_engine* e, const RunEnv& env, const MemoPlan& pl, in
   ma.delay = env.hdelay;
   const bool profile = env.timers();
   const bool tracing = env.profile == 2;
-  unsigned long long* d_trace = nullptr;
+  DevBuf<unsigned long long> d_trace;
   const int TS = std::min(max_ev, 4000);
   constexpr int kT = ksim_memo::kTrace;
   if (tracing) {
-    KSIM_HIP(hipMalloc(&d_trace, sizeof(unsigned long long) * kT * (size_t)pl.nwg * TS));
-    KSIM_HIP(hipMemsetAsync(d_trace, 0, sizeof(unsigned long long) * kT * (size_t)pl.nwg * TS, st));
-    ma.trace = d_trace;
+    if ((rc = d_trace.alloc(kT * (size_t)pl.nwg * TS))) return rc;
+    if ((rc = d_trace.zero(st))) return rc;
+    ma.trace = d_trace.p;
     ma.trace_steps = TS;
   }
   if (profile) {
@@ -2601,7 +2601,7 @@ static int launch_memo(ksim_engine* e, const RunEnv& env, const MemoPlan& pl, in
   }
   // the general instantiation for the profile / trace / deletes / no score table, else the lean one (with the
   // report's stores when the report is on)
-  const bool general = profile || tracing || !e->d_th ||
+  const bool general = profile || tracing || !e->d_th.p ||
                        std::any_of(e->mplan_reps.begin(), e->mplan_reps.end(), [&](int r) { return (bool)e->has_delete[r]; });
   // the hdelay test knob: the lean kernel with the stress delays compiled in (or the general one, which has them)
   using ksim_memo::k_memo;
@@ -2612,11 +2612,11 @@ static int launch_memo(ksim_engine* e, const RunEnv& env, const MemoPlan& pl, in
                   : general ? (const void*)k_memo<false, true>
                   : ma.delay ? (const void*)k_memo<false, false, true>
                   : e->report ? (const void*)k_memo<false, false, false, true> : (const void*)k_memo<false, false>;
-  const TypDev* tpp = e->d_tp;
+  const TypDev* tpp = e->d_tp.p;
   rc = launch_persistent(f, pl.nwg, ksim_memo::kMBlock, pl.lds, st, e->coop && pl.K > 1 && !started, ma, tpp);
   if (rc) return rc;
   hipLaunchKernelGGL(ksim_memo::k_memo_finish, dim3((unsigned)((stride + 255) / 256), (unsigned)Rg), dim3(256), 0, st,
-                     e->d_reps, (const int*)(e->d_replist + first), e->N);
+                     e->d_reps.p, (const int*)(e->d_replist.p + first), e->N);
   KSIM_HIP(hipGetLastError());
   if (tracing) {
     // per step: owner's start -> publish, publish -> each other workgroup's receive, receive -> start
@@ -2624,8 +2624,8 @@ static int launch_memo(ksim_engine* e, const RunEnv& env, const MemoPlan& pl, in
     KSIM_HIP(hipStreamSynchronize(st));
     const int K = pl.Kr[0];
     std::vector<unsigned long long> h((size_t)kT * pl.nwg * TS);
-    KSIM_HIP(hipMemcpy(h.data(), d_trace, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
-    KSIM_HIP(hipFree(d_trace));
+    KSIM_HIP(hipMemcpy(h.data(), d_trace.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
+    d_trace.release();
     std::vector<int> evo((size_t)TS);
     KSIM_HIP(hipMemcpy(evo.data(), e->d_m_evo.p, sizeof(int) * TS, hipMemcpyDeviceToHost));
     auto at = [&](int w, int s, int k) { return (double)h[((size_t)w * TS + s) * kT + k]; };
@@ -2711,8 +2711,8 @@ static int hmemo_init_keys(ksim_engine* e, int Rg, int first, hipStream_t st, in
   const HPlan& pl = *e->hplan;
   HInitArgs ia;
   ia.roff = roff;
-  ia.reps = e->d_reps;
-  ia.rep_list = e->d_replist + first;
+  ia.reps = e->d_reps.p;
+  ia.rep_list = e->d_replist.p + first;
   ia.N = e->N;
   ia.Npad = pl.Npad;
   ia.nb = pl.nb;
@@ -2731,18 +2731,18 @@ static int hmemo_init_keys(ksim_engine* e, int Rg, int first, hipStream_t st, in
   ia.l1 = e->d_h_l1.p;
   ia.l2 = pl.l2 ? e->d_h_l2.p : nullptr;
   ia.cnt = e->d_h_cnt.p;
-  ia.th = e->d_th;
+  ia.th = e->d_th.p;
   ia.mtoff = pl.Mtab > 0 ? e->d_h_mtoff.p : nullptr;
   ia.na = pl.Mtab > 0 ? e->d_h_na.p : nullptr;
   ia.Mslots = pl.Mslots;
   if (pl.Mtab > 0) {
     hipLaunchKernelGGL(k_hinit_na, dim3((unsigned)((kNaStride + 255) / 256), (unsigned)pl.Mslots, (unsigned)Rg), dim3(256), 0,
-                       st, ia, (const TypDev*)e->d_tp);
+                       st, ia, (const TypDev*)e->d_tp.p);
     KSIM_HIP(hipGetLastError());
   }
   KSIM_HIP(hipMemsetAsync(e->d_h_cnt.p, 0, sizeof(int) * (size_t)Rg * pl.Cmax, st));
   hipLaunchKernelGGL(k_hinit_gk, dim3((unsigned)((pl.Smax + 255) / 256), (unsigned)pl.Gmax, (unsigned)Rg), dim3(256), 0,
-                     st, ia, (const TypDev*)e->d_tp);
+                     st, ia, (const TypDev*)e->d_tp.p);
   KSIM_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_hinit_keys, dim3((unsigned)((pl.Npad + 255) / 256), (unsigned)pl.Cmax, (unsigned)Rg), dim3(256), 0,
                      st, ia);
@@ -2758,8 +2758,8 @@ static ksim_hmemo::HMemoArgs hmemo_args(ksim_engine* e, const RunEnv& env, int f
   const HPlan& pl = *e->hplan;
   HMemoArgs ma;
   std::memset(&ma, 0, sizeof ma);  // every field a caller does not set (the gate, profile, exchange pointers) is null
-  ma.reps = e->d_reps;
-  ma.rep_list = e->d_replist + first;
+  ma.reps = e->d_reps.p;
+  ma.rep_list = e->d_replist.p + first;
   ma.Mtab = pl.Mtab;
   ma.Mslots = pl.Mslots;
   ma.mtoff = pl.Mtab > 0 ? e->d_h_mtoff.p : nullptr;
@@ -2780,18 +2780,18 @@ static ksim_hmemo::HMemoArgs hmemo_args(ksim_engine* e, const RunEnv& env, int f
   ma.l1 = e->d_h_l1.p;
   ma.l2 = pl.l2 ? e->d_h_l2.p : nullptr;
   ma.cnt0 = e->d_h_cnt.p;
-  ma.th = e->d_th;
+  ma.th = e->d_th.p;
   ma.prof = nullptr;
   ma.K = pl.K;
   ma.S = pl.S;
   ma.nbw = pl.nbw;
-  ma.gran = e->d_gran;
-  ma.fail = e->d_fail;
+  ma.gran = e->d_gran.p;
+  ma.fail = e->d_fail.p;
   ma.hist = nullptr;
   ma.roff = 0;
   ma.wbase = 0;
   ma.Ktot = pl.K;
-  ma.tp = e->d_tp;
+  ma.tp = e->d_tp.p;
   ma.npeer = 0;
   ma.epoch = 0;
   {
@@ -2833,7 +2833,7 @@ static int launch_hmemo(ksim_engine* e, const RunEnv& env, int Rg, int first, in
       if (rc) return rc;
       ma.hist = e->d_h_hist.p;
     }
-    KSIM_HIP(hipMemsetAsync(e->d_gran, 0, sizeof(unsigned long long) * (size_t)Rg * 2 * pl.K * 2, st));
+    KSIM_HIP(hipMemsetAsync(e->d_gran.p, 0, sizeof(unsigned long long) * (size_t)Rg * 2 * pl.K * 2, st));
   }
   const bool profile = env.timers();
   if (profile) {
@@ -2857,11 +2857,11 @@ static int launch_hmemo(ksim_engine* e, const RunEnv& env, int Rg, int first, in
   }
   if (ma.started && Rg > resident_cap(e, f, pl.lds)) ma.started = nullptr;
   if (gated) *gated = ma.started != nullptr;
-  const TypDev* tpp = e->d_tp;
+  const TypDev* tpp = e->d_tp.p;
   const int lrc = launch_persistent(f, Rg * pl.K, kHBlock, pl.lds, st, e->coop && pl.K > 1, ma, tpp);
   if (lrc) return lrc;
   hipLaunchKernelGGL(ksim_memo::k_memo_finish, dim3((unsigned)((stride + 255) / 256), (unsigned)Rg), dim3(256), 0, st,
-                     e->d_reps, (const int*)(e->d_replist + first), e->N);
+                     e->d_reps.p, (const int*)(e->d_replist.p + first), e->N);
   KSIM_HIP(hipGetLastError());
   if (profile) {
     // per workgroup phase sums; refresh phases 0-4 run on one workgroup per step (the owner of the
@@ -2939,6 +2939,90 @@ int ksim_device_count(void) {
   return c;
 }
 
+// ksim_engine_create, step 1: the configuration, the device's properties and the process's knobs.
+static int read_config(ksim_engine* e, const ksim_config* cfg, int dev, int n_nodes, int n_replicas) {
+  e->device = dev;
+  e->N = n_nodes;
+  e->R = n_replicas;
+  if (cfg && cfg->nodes_per_block > 0) e->NB = std::min(cfg->nodes_per_block, kNBMax);
+  if (cfg && cfg->steps_per_graph > 0) e->K = cfg->steps_per_graph;
+  if (cfg) e->run_mode = cfg->run_mode, e->wgs_req = cfg->wgs_per_replica;
+  hipDeviceProp_t prop;
+  KSIM_HIP(hipGetDeviceProperties(&prop, dev));
+  e->cus = prop.multiProcessorCount;
+  // KSIM_CUS: use at most this many CUs for co-resident persistent grids (a device shared with
+  // another process; also the tests' way to exercise the residency checks)
+  if (const char* c = std::getenv("KSIM_CUS")) e->cus = std::max(1, std::min(e->cus, std::atoi(c)));
+  // KSIM_COOP=0: launch K > 1 grids with hipLaunchKernel (the grid is still capped by resident_cap);
+  // the profiler passes of scripts/profile_config.sh use it -- rocprofv3 7.2 faults at process exit
+  // after a cooperative launch
+  if (const char* c = std::getenv("KSIM_COOP")) e->coop = std::atoi(c) != 0;
+  // KSIM_VARIANT scan1: single-workgroup cheap-policy groups on k_scan1 with the records in VGPRs (2, default),
+  // in LDS (1), or on k_replay (0) -- A/B switches
+  e->scan1 = (int)variant("scan1", 2);
+  e->bpr = (n_nodes + e->NB - 1) / e->NB;
+  e->tags_stride = (size_t)n_nodes * kTagStride + (size_t)n_nodes * 2;  // + int rank2idx[N]
+  return KSIM_OK;
+}
+
+// Step 2: the stream, the timing events and the buffers whose size the node and replica counts fix, by size; the
+// cluster state, the capacities and the power model start zeroed.
+static int alloc_fixed(ksim_engine* e) {
+  const size_t n = (size_t)e->N, r = (size_t)e->R, nr = n * r, tags = e->tags_stride * r;
+  int rc = e->stream.ensure();  // after the first failure the rest does nothing
+  const auto alloc = [&](size_t count, auto&... buf) { ((rc = rc ? rc : buf.alloc(count)), ...); };
+  const auto zero = [&](auto&... buf) { ((rc = rc ? rc : buf.zero(e->stream)), ...); };
+  alloc(nr, e->d_nodes, e->d_nodes_init, e->d_cap, e->d_mcap, e->d_last, e->d_cpum, e->d_pws);
+  alloc(tags, e->d_tags, e->d_tags_init);
+  alloc(r, e->d_acc, e->d_reps, e->d_replist, e->d_pw);
+  alloc(n, e->d_feas, e->d_score, e->d_gpu);
+  alloc(4, e->d_base, e->d_scratch);
+  alloc(1, e->d_pod, e->d_res1, e->d_fail);
+  alloc(kMaxTypical * r, e->d_tp);
+  alloc(r * 2 * ksim_replay::kMaxK * ksim_replay::kGranW, e->d_gran);
+  zero(e->d_nodes, e->d_nodes_init, e->d_tags, e->d_tags_init, e->d_cap, e->d_mcap, e->d_pw, e->d_cpum);
+  for (DevEvent* ev : {&e->ev0, &e->ev1, &e->ev_mid}) rc = rc ? rc : ev->ensure();
+  return rc;
+}
+
+// Step 3: the per-replica host state, each replica's view of the buffers, and the empty accumulators.
+static int init_replicas(ksim_engine* e) {
+  const int R = e->R;
+  const size_t n = (size_t)e->N;
+  const auto per_replica = [R](auto&... v) { (v.resize(R), ...); };  // empty buffers, zero counts
+  per_replica(e->reps, e->h_nodes, e->h_rec, e->h_cls, e->h_tp, e->h_cls_n, e->h_ev_cls, e->go_state, e->d_ev, e->d_res,
+              e->d_snap, e->d_prev, e->d_rep, e->n_events, e->has_delete, e->wgs_hint, e->nt, e->total_gpus, e->pw_set);
+  for (int r = 0; r < R; ++r) {
+    ReplicaDev& rp = e->reps[r];
+    std::memset(&rp, 0, sizeof rp);
+    rp.policy = POL_FGD;
+    rp.gpusel = SEL_FGD;
+    rp.tp = e->d_tp.p + (size_t)r * kMaxTypical;
+    rp.nodes = e->d_nodes.p + r * n;
+    rp.n_local = e->N;
+    rp.tags = e->d_tags.p + r * e->tags_stride;
+    rp.cap = e->d_cap.p + r * n;
+    rp.mcap = e->d_mcap.p + r * n;
+    rp.init = e->d_nodes_init.p + r * n;
+    rp.last = e->d_last.p + r * n;
+    rp.pw = e->d_pw.p + r;
+    rp.cpum = e->d_cpum.p + r * n;
+    rp.pws = e->d_pws.p + r * n;
+    rp.w_pwr = 1000;
+  }
+  Accum none;
+  std::memset(&none, 0, sizeof none);
+  none.lo = 0x7fffffff, none.hi = -1;
+  const std::vector<Accum> acc(R, none);
+  int rc = e->d_acc.upload(acc, e->stream);
+  if (!rc) rc = upload_reps(e);
+  if (rc) return rc;
+  KSIM_HIP(hipStreamSynchronize(e->stream));  // `acc` is pageable
+  return KSIM_OK;
+}
+
+// All or nothing: the engine is handed out only when every step succeeded; a failing step destroys it with
+// whatever the steps before it made.
 int ksim_engine_create(const ksim_config* cfg, int n_nodes, int n_replicas, ksim_engine** out) {
   if (!out || n_nodes <= 0 || n_replicas <= 0) return KSIM_EINVAL;
   *out = nullptr;
@@ -2948,168 +3032,26 @@ int ksim_engine_create(const ksim_config* cfg, int n_nodes, int n_replicas, ksim
   int rc = check_gfx950(dev);
   if (rc) return rc;
   KSIM_HIP(hipSetDevice(dev));
-  ksim_engine* e = new ksim_engine();
-  e->device = dev;
-  e->N = n_nodes;
-  e->R = n_replicas;
-  if (cfg && cfg->nodes_per_block > 0) e->NB = std::min(cfg->nodes_per_block, kNBMax);
-  if (cfg && cfg->steps_per_graph > 0) e->K = cfg->steps_per_graph;
-  if (cfg) {
-    e->run_mode = cfg->run_mode;
-    e->wgs_req = cfg->wgs_per_replica;
-  }
-  {
-    hipDeviceProp_t prop;
-    KSIM_HIP(hipGetDeviceProperties(&prop, dev));
-    e->cus = prop.multiProcessorCount;
-    // KSIM_CUS: use at most this many CUs for co-resident persistent grids (a device shared with
-    // another process; also the tests' way to exercise the residency checks)
-    if (const char* c = std::getenv("KSIM_CUS")) e->cus = std::max(1, std::min(e->cus, std::atoi(c)));
-    // KSIM_COOP=0: launch K > 1 grids with hipLaunchKernel (the grid is still capped by resident_cap);
-    // the profiler passes of scripts/profile_config.sh use it -- rocprofv3 7.2 faults at process exit
-    // after a cooperative launch
-    if (const char* c = std::getenv("KSIM_COOP")) e->coop = std::atoi(c) != 0;
-    // KSIM_VARIANT scan1: single-workgroup cheap-policy groups on k_scan1 with the records in VGPRs (2, default),
-    // in LDS (1), or on k_replay (0) -- A/B switches
-    e->scan1 = (int)variant("scan1", 2);
-  }
-  e->bpr = (n_nodes + e->NB - 1) / e->NB;
-  e->tags_stride = (size_t)n_nodes * kTagStride + (size_t)n_nodes * 2;  // + int rank2idx[N]
-  KSIM_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-  KSIM_HIP(hipMalloc(&e->d_nodes, sizeof(NodeRec) * (size_t)n_nodes * n_replicas));
-  KSIM_HIP(hipMalloc(&e->d_tags, sizeof(uint16_t) * e->tags_stride * n_replicas));
-  KSIM_HIP(hipMalloc(&e->d_nodes_init, sizeof(NodeRec) * (size_t)n_nodes * n_replicas));
-  KSIM_HIP(hipMalloc(&e->d_tags_init, sizeof(uint16_t) * e->tags_stride * n_replicas));
-  KSIM_HIP(hipMemset(e->d_nodes, 0, sizeof(NodeRec) * (size_t)n_nodes * n_replicas));
-  KSIM_HIP(hipMemset(e->d_nodes_init, 0, sizeof(NodeRec) * (size_t)n_nodes * n_replicas));
-  KSIM_HIP(hipMemset(e->d_tags_init, 0, sizeof(uint16_t) * e->tags_stride * n_replicas));
-  KSIM_HIP(hipMalloc(&e->d_tp, sizeof(TypDev) * kMaxTypical * (size_t)n_replicas));
-  KSIM_HIP(hipMalloc(&e->d_acc, sizeof(Accum) * (size_t)n_replicas));
-  KSIM_HIP(hipMalloc(&e->d_reps, sizeof(ReplicaDev) * (size_t)n_replicas));
-  KSIM_HIP(hipMalloc(&e->d_base, sizeof(int) * 4));
-  KSIM_HIP(hipMalloc(&e->d_scratch, sizeof(int) * 4));
-  KSIM_HIP(hipMalloc(&e->d_pod, sizeof(PodDev)));
-  KSIM_HIP(hipMalloc(&e->d_res1, sizeof(ResultDev)));
-  KSIM_HIP(hipMalloc(&e->d_feas, (size_t)n_nodes));
-  KSIM_HIP(hipMalloc(&e->d_score, sizeof(int32_t) * n_nodes));
-  KSIM_HIP(hipMalloc(&e->d_gpu, sizeof(int32_t) * n_nodes));
-  KSIM_HIP(hipMalloc(&e->d_gran, sizeof(unsigned long long) * (size_t)n_replicas * 2 * ksim_replay::kMaxK *
-                                     ksim_replay::kGranW));
-  KSIM_HIP(hipMalloc(&e->d_fail, sizeof(int)));
-  KSIM_HIP(hipMalloc(&e->d_replist, sizeof(int) * (size_t)n_replicas));
-  KSIM_HIP(hipMalloc(&e->d_cap, sizeof(int32_t) * (size_t)n_nodes * n_replicas));
-  KSIM_HIP(hipMalloc(&e->d_mcap, sizeof(int32_t) * (size_t)n_nodes * n_replicas));
-  KSIM_HIP(hipMalloc(&e->d_pw, sizeof(PowerDev) * (size_t)n_replicas));
-  KSIM_HIP(hipMalloc(&e->d_cpum, (size_t)n_nodes * n_replicas));
-  KSIM_HIP(hipMalloc(&e->d_pws, sizeof(int2) * (size_t)n_nodes * n_replicas));
-  KSIM_HIP(hipMemset(e->d_pw, 0, sizeof(PowerDev) * (size_t)n_replicas));
-  KSIM_HIP(hipMemset(e->d_cpum, 0, (size_t)n_nodes * n_replicas));
-  e->pw_set.assign(n_replicas, 0);
-  KSIM_HIP(hipMalloc(&e->d_last, sizeof(int32_t) * (size_t)n_nodes * n_replicas));
-  KSIM_HIP(hipMemset(e->d_cap, 0, sizeof(int32_t) * (size_t)n_nodes * n_replicas));
-  KSIM_HIP(hipMemset(e->d_mcap, 0, sizeof(int32_t) * (size_t)n_nodes * n_replicas));
-  KSIM_HIP(hipMemset(e->d_tags, 0, sizeof(uint16_t) * e->tags_stride * n_replicas));
-  std::vector<Accum> acc(n_replicas);
-  for (auto& a : acc) {
-    std::memset(&a, 0, sizeof a);
-    a.lo = 0x7fffffff;
-    a.hi = -1;
-  }
-  KSIM_HIP(hipMemcpy(e->d_acc, acc.data(), sizeof(Accum) * n_replicas, hipMemcpyHostToDevice));
-  e->reps.resize(n_replicas);
-  e->h_nodes.resize(n_replicas);
-  e->h_rec.resize(n_replicas);
-  e->d_ev.assign(n_replicas, nullptr);
-  e->d_res.assign(n_replicas, nullptr);
-  e->n_events.assign(n_replicas, 0);
-  e->has_delete.assign(n_replicas, 0);
-  e->wgs_hint.assign(n_replicas, 0);
-  e->go_state.assign(n_replicas, {});
-  e->h_cls.resize(n_replicas);
-  e->h_tp.resize(n_replicas);
-  e->h_cls_n.resize(n_replicas);
-  e->h_ev_cls.resize(n_replicas);
-  e->nt.assign(n_replicas, 0);
-  e->d_snap.assign(n_replicas, nullptr);
-  e->d_prev.assign(n_replicas, nullptr);
-  e->d_rep.assign(n_replicas, nullptr);
-  e->total_gpus.assign(n_replicas, 0);
-  for (int r = 0; r < n_replicas; ++r) {
-    ReplicaDev& rp = e->reps[r];
-    std::memset(&rp, 0, sizeof rp);
-    rp.policy = POL_FGD;
-    rp.gpusel = SEL_FGD;
-    rp.tp = e->d_tp + (size_t)r * kMaxTypical;
-    rp.nodes = e->d_nodes + (size_t)r * n_nodes;
-    rp.n_local = n_nodes;
-    rp.tags = e->d_tags + (size_t)r * e->tags_stride;
-    rp.cap = e->d_cap + (size_t)r * n_nodes;
-    rp.mcap = e->d_mcap + (size_t)r * n_nodes;
-    rp.init = e->d_nodes_init + (size_t)r * n_nodes;
-    rp.last = e->d_last + (size_t)r * n_nodes;
-    rp.pw = e->d_pw + r;
-    rp.cpum = e->d_cpum + (size_t)r * n_nodes;
-    rp.pws = e->d_pws + (size_t)r * n_nodes;
-    rp.w_pwr = 1000;
-  }
-  KSIM_HIP(hipEventCreate(&e->ev0));
-  KSIM_HIP(hipEventCreate(&e->ev1));
-  KSIM_HIP(hipEventCreate(&e->ev_mid));
-  rc = upload_reps(e);
-  if (rc) return rc;
-  KSIM_HIP(hipStreamSynchronize(e->stream));
-  *out = e;
+  auto e = std::make_unique<ksim_engine>();
+  if ((rc = read_config(e.get(), cfg, dev, n_nodes, n_replicas))) return rc;
+  if ((rc = alloc_fixed(e.get()))) return rc;
+  if ((rc = init_replicas(e.get()))) return rc;
+  *out = e.release();
   return KSIM_OK;
 }
 
-void ksim_engine_destroy(ksim_engine* e) {
-  if (!e) return;
-  (void)hipSetDevice(e->device);
-  // drain every stream the engine launched on before anything they use is freed or destroyed: no
-  // dispatch (or a profiler's completion callback on it) may outlive its buffers, streams or graph
-  for (int i = 0; i < ksim_engine::kSide; ++i)
-    if (e->side[i]) (void)hipStreamSynchronize(e->side[i]);
-  if (e->stream) (void)hipStreamSynchronize(e->stream);
-  if (e->graph) (void)hipGraphExecDestroy(e->graph);
-  for (auto p : e->d_ev) (void)hipFree(p);
-  for (auto p : e->d_res) (void)hipFree(p);
-  for (auto p : e->d_snap) (void)hipFree(p);
-  for (auto p : e->d_prev) (void)hipFree(p);
-  for (auto p : e->d_rep) (void)hipFree(p);
-  // the plain pointers and the growable buffers, in the order they were always freed in
-  release_all(e->d_nodes, e->d_tags, e->d_nodes_init, e->d_tags_init, e->d_tp, e->d_acc, e->d_reps, e->d_base,
-              e->d_scratch, e->d_pod, e->d_res1, e->d_feas, e->d_score, e->d_gpu, e->d_gran, e->d_hist, e->d_fail,
-              e->d_prof, e->d_replist, e->d_cap, e->d_mcap, e->d_last, e->d_send, e->d_recv, e->d_ptrs, e->d_m_pod,
-              e->d_m_owner, e->d_m_wgcls, e->d_m_wgref, e->d_m_wggrp, e->d_win, e->d_m_evo, e->d_th, e->d_pw,
-              e->d_cpum, e->d_pws, e->d_m_evcls, e->d_topg, e->d_m_hkeys, e->d_m_wgmap, e->d_h_cg, e->d_h_cls,
-              e->d_h_cgrp, e->d_h_gpod, e->d_h_evc, e->d_h_st, e->d_h_ns, e->d_h_nstate, e->d_h_gsc, e->d_h_mtoff,
-              e->d_h_mtab, e->d_h_na, e->d_h_keys, e->d_h_l1, e->d_h_l2, e->d_h_cnt, e->d_h_prof, e->d_h_hist,
-              e->d_go, e->d_ggran, e->d_hgargs, e->d_rgran, e->d_rgreps, e->d_rglist, e->d_done, e->d_ragg,
-              e->d_ds_eval, e->d_ds_gone, e->d_ds_plist, e->d_ds_vict, e->d_ds_cnt, e->d_ds_eoff, e->d_ds_tab);
-  if (e->ev_ds0) (void)hipEventDestroy(e->ev_ds0);
-  if (e->ev_ds1) (void)hipEventDestroy(e->ev_ds1);
-  for (int i = 0; i < ksim_engine::kSide; ++i) {
-    if (e->side[i]) (void)hipStreamDestroy(e->side[i]);
-    if (e->side_ev[i]) (void)hipEventDestroy(e->side_ev[i]);
-    if (e->tev_side[i]) (void)hipEventDestroy(e->tev_side[i]);
-  }
-  if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-  if (e->ev_ovl) (void)hipEventDestroy(e->ev_ovl);
-  if (e->ev0) (void)hipEventDestroy(e->ev0);
-  if (e->ev1) (void)hipEventDestroy(e->ev1);
-  if (e->ev_mid) (void)hipEventDestroy(e->ev_mid);
-  if (e->comm) destroy_comm(e->comm);
-  for (size_t q = 0; q < e->peers.size(); ++q)
-    if (e->peer_opened[q]) (void)hipIpcCloseMemHandle(e->peers[q]);
-  if (e->d_pgran) (void)hipFree(e->d_pgran);
-  if (e->tev_fork) (void)hipEventDestroy(e->tev_fork);
-  for (hipEvent_t v : e->grp_rev) (void)hipEventDestroy(v);
-  if (e->h_started) (void)hipHostFree(e->h_started);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
-  delete e->mplan;
-  delete e->hplan;
-  delete e;
+ksim_engine::~ksim_engine() {
+  (void)hipSetDevice(device);
+  for (DevStream& s : side)
+    if (s) (void)hipStreamSynchronize(s);
+  if (stream) (void)hipStreamSynchronize(stream);
+  graph.reset();
+  if (comm) destroy_comm(comm);
+  for (size_t q = 0; q < peers.size(); ++q)
+    if (peer_opened[q]) (void)hipIpcCloseMemHandle(peers[q]);
 }
+
+void ksim_engine_destroy(ksim_engine* e) { if (e) delete e; }
 
 static int to_pod_dev(const ksim_pod& s, PodDev* d) {
   if (s.gpu_milli < 0 || s.gpu_milli > kMilli || s.gpu_count < 0 || s.gpu_count > kMaxGpu) return KSIM_ERANGE;
@@ -3186,17 +3128,17 @@ int ksim_engine_set_nodes(ksim_engine* e, int replica, const ksim_node* nodes) {
   e->ran = e->ds_done = false;
   e->total_gpus[replica] = gpus;
   KSIM_HIP(hipSetDevice(e->device));
-  KSIM_HIP(hipMemcpyAsync(e->d_cap + (size_t)replica * e->N, cap.data(), sizeof(int32_t) * e->N, hipMemcpyHostToDevice,
+  KSIM_HIP(hipMemcpyAsync(e->d_cap.p + (size_t)replica * e->N, cap.data(), sizeof(int32_t) * e->N, hipMemcpyHostToDevice,
                           e->stream));
-  KSIM_HIP(hipMemcpyAsync(e->d_mcap + (size_t)replica * e->N, mcap.data(), sizeof(int32_t) * e->N, hipMemcpyHostToDevice,
+  KSIM_HIP(hipMemcpyAsync(e->d_mcap.p + (size_t)replica * e->N, mcap.data(), sizeof(int32_t) * e->N, hipMemcpyHostToDevice,
                           e->stream));
-  KSIM_HIP(hipMemcpyAsync(e->d_cpum + (size_t)replica * e->N, cpum.data(), e->N, hipMemcpyHostToDevice, e->stream));
+  KSIM_HIP(hipMemcpyAsync(e->d_cpum.p + (size_t)replica * e->N, cpum.data(), e->N, hipMemcpyHostToDevice, e->stream));
   KSIM_HIP(hipMemcpyAsync(e->reps[replica].nodes, h.data(), sizeof(NodeRec) * e->N, hipMemcpyHostToDevice, e->stream));
-  KSIM_HIP(hipMemcpyAsync(e->d_tags + (size_t)replica * e->tags_stride, tags.data(), sizeof(uint16_t) * e->tags_stride,
+  KSIM_HIP(hipMemcpyAsync(e->d_tags.p + (size_t)replica * e->tags_stride, tags.data(), sizeof(uint16_t) * e->tags_stride,
                           hipMemcpyHostToDevice, e->stream));
-  KSIM_HIP(hipMemcpyAsync(e->d_nodes_init + (size_t)replica * e->N, h.data(), sizeof(NodeRec) * e->N,
+  KSIM_HIP(hipMemcpyAsync(e->d_nodes_init.p + (size_t)replica * e->N, h.data(), sizeof(NodeRec) * e->N,
                           hipMemcpyHostToDevice, e->stream));
-  KSIM_HIP(hipMemcpyAsync(e->d_tags_init + (size_t)replica * e->tags_stride, tags.data(),
+  KSIM_HIP(hipMemcpyAsync(e->d_tags_init.p + (size_t)replica * e->tags_stride, tags.data(),
                           sizeof(uint16_t) * e->tags_stride, hipMemcpyHostToDevice, e->stream));
   KSIM_HIP(hipStreamSynchronize(e->stream));
   return KSIM_OK;
@@ -3230,7 +3172,7 @@ int ksim_engine_set_typical(ksim_engine* e, int replica, const ksim_typical* tp,
   if ((int)h.size() > kMaxTypical) return KSIM_ERANGE;
   KSIM_HIP(hipSetDevice(e->device));
   if (!h.empty())
-    KSIM_HIP(hipMemcpyAsync(e->d_tp + (size_t)replica * kMaxTypical, h.data(), sizeof(TypDev) * h.size(),
+    KSIM_HIP(hipMemcpyAsync(e->d_tp.p + (size_t)replica * kMaxTypical, h.data(), sizeof(TypDev) * h.size(),
                             hipMemcpyHostToDevice, e->stream));
   e->reps[replica].nt = (int)h.size();
   e->reps[replica].ncpu = (int)cpu.size();
@@ -3327,7 +3269,7 @@ int ksim_engine_set_power_model(ksim_engine* e, int replica, const ksim_power_mo
   for (int c = 0; c < kMaxCpuModels; ++c)
     if (((pm->cpu_valid >> c) & 1u) && !(pm->cpu_cores[c] > 0)) return KSIM_ERANGE;
   KSIM_HIP(hipSetDevice(e->device));
-  KSIM_HIP(hipMemcpyAsync(e->d_pw + replica, pm, sizeof(PowerDev), hipMemcpyHostToDevice, e->stream));
+  KSIM_HIP(hipMemcpyAsync(e->d_pw.p + replica, pm, sizeof(PowerDev), hipMemcpyHostToDevice, e->stream));
   KSIM_HIP(hipStreamSynchronize(e->stream));
   e->pw_set[replica] = 1;
   e->reps[replica].has_pw = 1;
@@ -3346,8 +3288,8 @@ static bool any_pwr(const ksim_engine* e) {
 static StepArgs base_args(ksim_engine* e) {
   StepArgs a;
   std::memset(&a, 0, sizeof a);
-  a.reps = e->d_reps;
-  a.acc = e->d_acc;
+  a.reps = e->d_reps.p;
+  a.acc = e->d_acc.p;
   a.N = e->N;
   a.NB = e->NB;
   a.bpr = e->bpr;
@@ -3365,21 +3307,21 @@ int ksim_engine_filter_score(ksim_engine* e, int replica, const ksim_pod* pod, i
   if (e->reps[replica].policy == POL_PWR_FGD) return KSIM_ENOTSUP;
   if (is_pwr_policy(e->reps[replica].policy) && !e->pw_set[replica]) return KSIM_ESTATE;
   KSIM_HIP(hipSetDevice(e->device));
-  KSIM_HIP(hipMemcpyAsync(e->d_pod, &p, sizeof p, hipMemcpyHostToDevice, e->stream));
+  KSIM_HIP(hipMemcpyAsync(e->d_pod.p, &p, sizeof p, hipMemcpyHostToDevice, e->stream));
   StepArgs a = base_args(e);
   a.rep_first = replica;
   a.step_off = step;
-  a.pod_override = e->d_pod;
-  a.res_override = e->d_res1;
+  a.pod_override = e->d_pod.p;
+  a.res_override = e->d_res1.p;
   a.mode = 1;
-  a.out_feas = e->d_feas;
-  a.out_score = e->d_score;
-  a.out_gpu = e->d_gpu;
-  hipLaunchKernelGGL(k_step, dim3(e->bpr), dim3(kBlock), 0, e->stream, a, (const TypDev*)e->d_tp);
+  a.out_feas = e->d_feas.p;
+  a.out_score = e->d_score.p;
+  a.out_gpu = e->d_gpu.p;
+  hipLaunchKernelGGL(k_step, dim3(e->bpr), dim3(kBlock), 0, e->stream, a, (const TypDev*)e->d_tp.p);
   KSIM_HIP(hipGetLastError());
-  KSIM_HIP(hipMemcpyAsync(feasible, e->d_feas, e->N, hipMemcpyDeviceToHost, e->stream));
-  KSIM_HIP(hipMemcpyAsync(score, e->d_score, sizeof(int32_t) * e->N, hipMemcpyDeviceToHost, e->stream));
-  KSIM_HIP(hipMemcpyAsync(gpu_mask, e->d_gpu, sizeof(int32_t) * e->N, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipMemcpyAsync(feasible, e->d_feas.p, e->N, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipMemcpyAsync(score, e->d_score.p, sizeof(int32_t) * e->N, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipMemcpyAsync(gpu_mask, e->d_gpu.p, sizeof(int32_t) * e->N, hipMemcpyDeviceToHost, e->stream));
   KSIM_HIP(hipStreamSynchronize(e->stream));
   return KSIM_OK;
 }
@@ -3391,20 +3333,20 @@ int ksim_engine_schedule(ksim_engine* e, int replica, const ksim_pod* pod, int32
   if (rc) return rc;
   if (p.flags & kPodDelete) return KSIM_EINVAL;  // deletions go through ksim_engine_unreserve
   KSIM_HIP(hipSetDevice(e->device));
-  KSIM_HIP(hipMemcpyAsync(e->d_pod, &p, sizeof p, hipMemcpyHostToDevice, e->stream));
+  KSIM_HIP(hipMemcpyAsync(e->d_pod.p, &p, sizeof p, hipMemcpyHostToDevice, e->stream));
   StepArgs a = base_args(e);
   a.rep_first = replica;
   a.step_off = step;
-  a.pod_override = e->d_pod;
-  a.res_override = e->d_res1;
+  a.pod_override = e->d_pod.p;
+  a.res_override = e->d_res1.p;
   a.mode = 0;
   if (is_pwr_policy(e->reps[replica].policy) && !e->pw_set[replica]) return KSIM_ESTATE;
-  hipLaunchKernelGGL(k_step, dim3(e->bpr), dim3(kBlock), 0, e->stream, a, (const TypDev*)e->d_tp);
+  hipLaunchKernelGGL(k_step, dim3(e->bpr), dim3(kBlock), 0, e->stream, a, (const TypDev*)e->d_tp.p);
   if (is_pwr_policy(e->reps[replica].policy))
     hipLaunchKernelGGL(k_step_pwr, dim3(e->bpr), dim3(kBlock), 0, e->stream, a);
   KSIM_HIP(hipGetLastError());
   ResultDev r;
-  KSIM_HIP(hipMemcpyAsync(&r, e->d_res1, sizeof r, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipMemcpyAsync(&r, e->d_res1.p, sizeof r, hipMemcpyDeviceToHost, e->stream));
   KSIM_HIP(hipStreamSynchronize(e->stream));
   std::memcpy(out, &r, sizeof r);
   return KSIM_OK;
@@ -3416,10 +3358,10 @@ int ksim_engine_reserve(ksim_engine* e, int replica, const ksim_pod* pod, int no
   int rc = to_pod_dev(*pod, &p);
   if (rc) return rc;
   KSIM_HIP(hipSetDevice(e->device));
-  hipLaunchKernelGGL(k_reserve, dim3(1), dim3(64), 0, e->stream, e->d_reps, (const TypDev*)e->d_tp, replica, p, node, step, e->d_scratch, +1, -1);
+  hipLaunchKernelGGL(k_reserve, dim3(1), dim3(64), 0, e->stream, e->d_reps.p, (const TypDev*)e->d_tp.p, replica, p, node, step, e->d_scratch.p, +1, -1);
   KSIM_HIP(hipGetLastError());
   int m = 0;
-  KSIM_HIP(hipMemcpyAsync(&m, e->d_scratch, sizeof m, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipMemcpyAsync(&m, e->d_scratch.p, sizeof m, hipMemcpyDeviceToHost, e->stream));
   KSIM_HIP(hipStreamSynchronize(e->stream));
   *gpu_mask_out = m;
   return m < 0 ? KSIM_ESTATE : KSIM_OK;
@@ -3439,11 +3381,11 @@ int ksim_engine_unreserve(ksim_engine* e, int replica, const ksim_pod* pod, int 
   if ((p.milli == 0) != (gpu_mask == 0)) return KSIM_EINVAL;
   if (p.milli > 0 && __builtin_popcount((unsigned)gpu_mask) != p.num) return KSIM_EINVAL;
   KSIM_HIP(hipSetDevice(e->device));
-  hipLaunchKernelGGL(k_reserve, dim3(1), dim3(64), 0, e->stream, e->d_reps, (const TypDev*)e->d_tp, replica, p, node, 0, e->d_scratch, -1,
+  hipLaunchKernelGGL(k_reserve, dim3(1), dim3(64), 0, e->stream, e->d_reps.p, (const TypDev*)e->d_tp.p, replica, p, node, 0, e->d_scratch.p, -1,
                      (int)gpu_mask);
   KSIM_HIP(hipGetLastError());
   int m = 0;
-  KSIM_HIP(hipMemcpyAsync(&m, e->d_scratch, sizeof m, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipMemcpyAsync(&m, e->d_scratch.p, sizeof m, hipMemcpyDeviceToHost, e->stream));
   KSIM_HIP(hipStreamSynchronize(e->stream));
   return m < 0 ? KSIM_ESTATE : KSIM_OK;  // the node does not hold what the pod would release
 }
@@ -3460,11 +3402,11 @@ int ksim_engine_bind(ksim_engine* e, int replica, const ksim_pod* pod, int node,
   if ((p.milli == 0) != (gpu_mask == 0)) return KSIM_EINVAL;
   if (p.milli > 0 && __builtin_popcount((unsigned)gpu_mask) != p.num) return KSIM_EINVAL;
   KSIM_HIP(hipSetDevice(e->device));
-  hipLaunchKernelGGL(k_reserve, dim3(1), dim3(64), 0, e->stream, e->d_reps, (const TypDev*)e->d_tp, replica, p, node, 0,
-                     e->d_scratch, +1, (int)gpu_mask);
+  hipLaunchKernelGGL(k_reserve, dim3(1), dim3(64), 0, e->stream, e->d_reps.p, (const TypDev*)e->d_tp.p, replica, p, node, 0,
+                     e->d_scratch.p, +1, (int)gpu_mask);
   KSIM_HIP(hipGetLastError());
   int m = 0;
-  KSIM_HIP(hipMemcpyAsync(&m, e->d_scratch, sizeof m, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipMemcpyAsync(&m, e->d_scratch.p, sizeof m, hipMemcpyDeviceToHost, e->stream));
   KSIM_HIP(hipStreamSynchronize(e->stream));
   return m < 0 ? KSIM_ESTATE : KSIM_OK;  // a named device lacks the milli (the reference panics)
 }
@@ -3518,20 +3460,22 @@ int ksim_engine_load_events(ksim_engine* e, int replica, const ksim_pod* events,
     for (int i = 0; i < n; ++i) e->h_ev_cls[replica][i] = h[i].pad;
   }
   KSIM_HIP(hipSetDevice(e->device));
-  if (e->d_ev[replica]) { KSIM_HIP(hipFree(e->d_ev[replica])); e->d_ev[replica] = nullptr; }
-  if (e->d_res[replica]) { KSIM_HIP(hipFree(e->d_res[replica])); e->d_res[replica] = nullptr; }
+  // the replica's buffers afresh: a failed alloc leaves its buffer empty, so the replica points at live memory or at
+  // none, and has no events until both buffers are there
   const size_t ne = (size_t)std::max(n, 1);
-  KSIM_HIP(hipMalloc(&e->d_ev[replica], sizeof(PodDev) * ne));
-  KSIM_HIP(hipMalloc(&e->d_res[replica], sizeof(ResultDev) * ne));
-  if (n > 0) KSIM_HIP(hipMemcpyAsync(e->d_ev[replica], h.data(), sizeof(PodDev) * n, hipMemcpyHostToDevice, e->stream));
-  KSIM_HIP(hipMemsetAsync(e->d_res[replica], 0xff, sizeof(ResultDev) * ne, e->stream));
-  e->n_events[replica] = n;
+  DevBuf<PodDev>& ev = e->d_ev[replica];
+  DevBuf<ResultDev>& res = e->d_res[replica];
+  int rc = ev.alloc(ne);
+  if (!rc) rc = res.alloc(ne);
+  if (!rc) rc = res.fill(0xff, e->stream);
+  e->reps[replica].ev = ev.p;
+  e->reps[replica].res = res.p;
+  e->reps[replica].n_events = e->n_events[replica] = rc ? 0 : n;
+  if (rc) return rc;
+  if (n > 0) KSIM_HIP(hipMemcpyAsync(ev.p, h.data(), sizeof(PodDev) * n, hipMemcpyHostToDevice, e->stream));
   e->has_delete[replica] = false;
   for (int i = 0; i < n; ++i) e->has_delete[replica] = e->has_delete[replica] || events[i].is_delete;
-  e->reps[replica].ev = e->d_ev[replica];
-  e->reps[replica].res = e->d_res[replica];
-  e->reps[replica].n_events = n;
-  int rc = alloc_report(e, replica);
+  rc = alloc_report(e, replica);
   if (rc) return rc;
   rc = upload_reps(e);
   if (rc) return rc;
@@ -3541,31 +3485,25 @@ int ksim_engine_load_events(ksim_engine* e, int replica, const ksim_pod* events,
 
 // Every replica back to the cluster state given to set_nodes (device-to-device).
 static int reset_state(ksim_engine* e) {
-  KSIM_HIP(hipMemcpyAsync(e->d_nodes, e->d_nodes_init, sizeof(NodeRec) * (size_t)e->N * e->R, hipMemcpyDeviceToDevice,
+  KSIM_HIP(hipMemcpyAsync(e->d_nodes.p, e->d_nodes_init.p, sizeof(NodeRec) * (size_t)e->N * e->R, hipMemcpyDeviceToDevice,
                           e->stream));
-  KSIM_HIP(hipMemcpyAsync(e->d_tags, e->d_tags_init, sizeof(uint16_t) * e->tags_stride * e->R, hipMemcpyDeviceToDevice,
+  KSIM_HIP(hipMemcpyAsync(e->d_tags.p, e->d_tags_init.p, sizeof(uint16_t) * e->tags_stride * e->R, hipMemcpyDeviceToDevice,
                           e->stream));
   return KSIM_OK;
 }
 
 // Per-event report buffers of one replica (allocated while the report is enabled).
 static int alloc_report(ksim_engine* e, int r) {
-  ReplicaDev& rp = e->reps[r];
-  if (e->d_snap[r]) { KSIM_HIP(hipFree(e->d_snap[r])); e->d_snap[r] = nullptr; }
-  if (e->d_prev[r]) { KSIM_HIP(hipFree(e->d_prev[r])); e->d_prev[r] = nullptr; }
-  if (e->d_rep[r]) { KSIM_HIP(hipFree(e->d_rep[r])); e->d_rep[r] = nullptr; }
-  rp.snap = nullptr;
-  rp.prev = nullptr;
-  rp.rep = nullptr;
-  if (!e->report || !e->d_ev[r]) return KSIM_OK;
+  const bool on = e->report && e->d_ev[r].p;
   const size_t ne = (size_t)std::max(e->n_events[r], 1);
-  KSIM_HIP(hipMalloc(&e->d_snap[r], sizeof(NodeRec) * ne));
-  KSIM_HIP(hipMalloc(&e->d_prev[r], sizeof(int32_t) * ne));
-  KSIM_HIP(hipMalloc(&e->d_rep[r], sizeof(RepAcc) * ne));
-  rp.snap = e->d_snap[r];
-  rp.prev = e->d_prev[r];
-  rp.rep = e->d_rep[r];
-  return KSIM_OK;
+  int rc = on ? e->d_snap[r].alloc(ne) : KSIM_OK;
+  if (on && !rc) rc = e->d_prev[r].alloc(ne);
+  if (on && !rc) rc = e->d_rep[r].alloc(ne);
+  if (!on || rc) e->d_snap[r].release(), e->d_prev[r].release(), e->d_rep[r].release();  // all three or none
+  e->reps[r].snap = e->d_snap[r].p;
+  e->reps[r].prev = e->d_prev[r].p;
+  e->reps[r].rep = e->d_rep[r].p;
+  return rc;
 }
 
 // The per-event cluster report of every replica from the run's snapshots (ksim_report.hpp).
@@ -3574,7 +3512,7 @@ static int run_report(ksim_engine* e, int max_ev, hipStream_t st, const int* lis
   if (max_ev <= 0 || R <= 0) return KSIM_OK;
   const dim3 grid((unsigned)((max_ev + ksim_rep::kDeltaBlock - 1) / ksim_rep::kDeltaBlock), (unsigned)R);
   hipLaunchKernelGGL(ksim_rep::k_report_delta, grid, dim3(ksim_rep::kDeltaBlock), 0, st,
-                     (const ReplicaDev*)e->d_reps, (const TypDev*)e->d_tp, list);
+                     (const ReplicaDev*)e->d_reps.p, (const TypDev*)e->d_tp.p, list);
   KSIM_HIP(hipGetLastError());
   // the scan over B workgroups per replica when a few replicas would leave most CUs idle behind one workgroup's pass
   // (about a CU-full of workgroups, parts of >= 2048 events; KSIM_VARIANT report_parts=0: one workgroup each)
@@ -3584,15 +3522,15 @@ static int run_report(ksim_engine* e, int max_ev, hipStream_t st, const int* lis
     const int rc = e->d_ragg.ensure((size_t)e->R * ksim_rep::kScanPartsMax * 2 * ksim_rep::kFields);
     if (rc) return rc;
     hipLaunchKernelGGL(ksim_rep::k_report_part, dim3((unsigned)B, (unsigned)R), dim3(ksim_rep::kScanBlock), 0, st,
-                       (const ReplicaDev*)e->d_reps, (const TypDev*)e->d_tp, e->N, list, e->d_ragg.p);
+                       (const ReplicaDev*)e->d_reps.p, (const TypDev*)e->d_tp.p, e->N, list, e->d_ragg.p);
     KSIM_HIP(hipGetLastError());
     hipLaunchKernelGGL(ksim_rep::k_report_apply, dim3((unsigned)B, (unsigned)R), dim3(ksim_rep::kScanBlock), 0, st,
-                       (const ReplicaDev*)e->d_reps, e->N, list, (const __int128*)e->d_ragg.p);
+                       (const ReplicaDev*)e->d_reps.p, e->N, list, (const __int128*)e->d_ragg.p);
     KSIM_HIP(hipGetLastError());
     return KSIM_OK;
   }
   hipLaunchKernelGGL(ksim_rep::k_report_scan, dim3(R), dim3(ksim_rep::kScanBlock), 0, st,
-                     (const ReplicaDev*)e->d_reps, (const TypDev*)e->d_tp, e->N, list);
+                     (const ReplicaDev*)e->d_reps.p, (const TypDev*)e->d_tp.p, e->N, list);
   KSIM_HIP(hipGetLastError());
   return KSIM_OK;
 }
@@ -3646,8 +3584,8 @@ static int shard_local(ksim_engine* e, hipStream_t st, const int* base, int step
   a.base = base;
   a.step_off = step_off;
   a.mode = 2;
-  a.send = e->d_send;
-  hipLaunchKernelGGL(k_step, dim3(e->bpr), dim3(kBlock), 0, st, a, (const TypDev*)e->d_tp);
+  a.send = e->d_send.p;
+  hipLaunchKernelGGL(k_step, dim3(e->bpr), dim3(kBlock), 0, st, a, (const TypDev*)e->d_tp.p);
   KSIM_HIP(hipGetLastError());
   return KSIM_OK;
 }
@@ -3655,7 +3593,7 @@ static int shard_commit(ksim_engine* e, hipStream_t st, const int* base, int ste
   StepArgs a = base_args(e);
   a.base = base;
   a.step_off = step_off;
-  a.recv = e->d_recv;
+  a.recv = e->d_recv.p;
   a.world = e->shard_world;
   hipLaunchKernelGGL(k_shard_commit, dim3(1), dim3(64), 0, st, a);
   KSIM_HIP(hipGetLastError());
@@ -3663,14 +3601,14 @@ static int shard_commit(ksim_engine* e, hipStream_t st, const int* base, int ste
 }
 static int shard_exchange(ksim_engine* e, hipStream_t st) {
   if (e->comm) {
-    const ncclResult_t r = rccl()->all_gather(e->d_send, e->d_recv, 4, ncclUint64, e->comm, st);
+    const ncclResult_t r = rccl()->all_gather(e->d_send.p, e->d_recv.p, 4, ncclUint64, e->comm, st);
     if (r != ncclSuccess) {
       std::fprintf(stderr, "ksim: ncclAllGather failed: %s\n", rccl()->error_string(r));
       return KSIM_EHIP;
     }
     return KSIM_OK;
   }
-  KSIM_HIP(hipMemcpyAsync(e->d_recv, e->d_send, 4 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+  KSIM_HIP(hipMemcpyAsync(e->d_recv.p, e->d_send.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
   return KSIM_OK;
 }
 
@@ -3682,12 +3620,12 @@ static int run_sharded(ksim_engine* e, int max_ev) {
     const size_t rec = 4 * sizeof(unsigned long long);
     for (int s = 0; s < max_ev; ++s) {
       if ((rc = shard_local(e, e->stream, nullptr, s))) return rc;
-      KSIM_HIP(hipMemcpyAsync(e->h_send.data(), e->d_send, rec, hipMemcpyDeviceToHost, e->stream));
+      KSIM_HIP(hipMemcpyAsync(e->h_send.data(), e->d_send.p, rec, hipMemcpyDeviceToHost, e->stream));
       KSIM_HIP(hipStreamSynchronize(e->stream));
       if (e->xfn(e->h_send.data(), e->h_recv.data(), e->xuser) != 0) return KSIM_ESTATE;
       // the caller's gather must hold this shard's own record at its rank
       if (std::memcmp(e->h_recv.data() + 4 * (size_t)e->shard_rank, e->h_send.data(), rec) != 0) return KSIM_ESTATE;
-      KSIM_HIP(hipMemcpyAsync(e->d_recv, e->h_recv.data(), rec * (size_t)e->shard_world, hipMemcpyHostToDevice,
+      KSIM_HIP(hipMemcpyAsync(e->d_recv.p, e->h_recv.data(), rec * (size_t)e->shard_world, hipMemcpyHostToDevice,
                               e->stream));
       if ((rc = shard_commit(e, e->stream, nullptr, s))) return rc;
     }
@@ -3695,25 +3633,24 @@ static int run_sharded(ksim_engine* e, int max_ev) {
   }
   if (e->shard_world > 1 && !e->comm) return KSIM_ESTATE;  // in-process group: ksim_shard_group_run
   hipGraph_t g = nullptr;
-  hipGraphExec_t ge = nullptr;
+  GraphExec ge;
   const int K = std::min(e->K, std::max(max_ev, 1));
   if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
     bool ok = true;
     for (int i = 0; i < K && ok; ++i)
-      ok = shard_local(e, e->stream, e->d_base, i) == KSIM_OK && shard_exchange(e, e->stream) == KSIM_OK &&
-           shard_commit(e, e->stream, e->d_base, i) == KSIM_OK;
-    if (ok) hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, e->stream, e->d_base, K);
+      ok = shard_local(e, e->stream, e->d_base.p, i) == KSIM_OK && shard_exchange(e, e->stream) == KSIM_OK &&
+           shard_commit(e, e->stream, e->d_base.p, i) == KSIM_OK;
+    if (ok) hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, e->stream, e->d_base.p, K);
     const hipError_t ce = hipStreamEndCapture(e->stream, &g);
-    if (ok && ce == hipSuccess && hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) != hipSuccess) ge = nullptr;
+    if (ok && ce == hipSuccess && hipGraphInstantiate(&ge.h, g, nullptr, nullptr, 0) != hipSuccess) ge.h = nullptr;
     if (g) (void)hipGraphDestroy(g);
     (void)hipGetLastError();
   }
   if (ge) {
-    KSIM_HIP(hipMemsetAsync(e->d_base, 0, sizeof(int), e->stream));
+    KSIM_HIP(hipMemsetAsync(e->d_base.p, 0, sizeof(int), e->stream));
     for (int s0 = 0; s0 < max_ev; s0 += K) {
-      if (hipGraphLaunch(ge, e->stream) != hipSuccess) { (void)hipGraphExecDestroy(ge); return KSIM_EHIP; }
+      if (hipGraphLaunch(ge, e->stream) != hipSuccess) return KSIM_EHIP;
     }
-    (void)hipGraphExecDestroy(ge);
     return KSIM_OK;
   }
   for (int s = 0; s < max_ev; ++s) {
@@ -3727,20 +3664,20 @@ static int run_sharded(ksim_engine* e, int max_ev) {
 static int build_graph(ksim_engine* e) {
   const bool pwr = any_pwr(e);
   if (e->graph && e->graph_R == e->R && e->graph_pwr == pwr) return KSIM_OK;
-  if (e->graph) { (void)hipGraphExecDestroy(e->graph); e->graph = nullptr; }
+  e->graph.reset();
   hipGraph_t g;
   KSIM_HIP(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
   StepArgs a = base_args(e);
   a.rep_first = 0;
-  a.base = e->d_base;
+  a.base = e->d_base.p;
   for (int i = 0; i < e->K; ++i) {
     a.step_off = i;
-    hipLaunchKernelGGL(k_step, dim3(e->bpr * e->R), dim3(kBlock), 0, e->stream, a, (const TypDev*)e->d_tp);
+    hipLaunchKernelGGL(k_step, dim3(e->bpr * e->R), dim3(kBlock), 0, e->stream, a, (const TypDev*)e->d_tp.p);
     if (pwr) hipLaunchKernelGGL(k_step_pwr, dim3(e->bpr * e->R), dim3(kBlock), 0, e->stream, a);
   }
-  hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, e->stream, e->d_base, e->K);
+  hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, e->stream, e->d_base.p, e->K);
   KSIM_HIP(hipStreamEndCapture(e->stream, &g));
-  KSIM_HIP(hipGraphInstantiate(&e->graph, g, nullptr, nullptr, 0));
+  KSIM_HIP(hipGraphInstantiate(&e->graph.h, g, nullptr, nullptr, 0));
   KSIM_HIP(hipGraphDestroy(g));
   e->graph_R = e->R;
   e->graph_pwr = pwr;
@@ -4021,19 +3958,17 @@ static void note_launch(ksim_engine* e, const char* name, int K, int* replicas, 
 static int upload_go_states(ksim_engine* e, const RunPlan& plan) {
   if (plan.groups.empty() || plan.groups.back().kind != kPolRandomGo) return KSIM_OK;
   const size_t words = (size_t)e->R * ksim_random_go::kStateWords;
-  const int rc = e->d_go.ensure(words);
-  if (rc) return rc;
   std::vector<unsigned long long> h(words, 0ull);
   for (int r = 0; r < e->R; ++r)
     if (go_random(e, r))
       std::copy(e->go_state[r].begin(), e->go_state[r].end(), h.begin() + (size_t)r * ksim_random_go::kStateWords);
-  KSIM_HIP(hipMemcpyAsync(e->d_go.p, h.data(), sizeof(unsigned long long) * words, hipMemcpyHostToDevice, e->stream));
+  if (const int rc = e->d_go.upload(h, e->stream)) return rc;
   KSIM_HIP(hipStreamSynchronize(e->stream));  // h is a local
   return KSIM_OK;
 }
 
 static int launch_random_go(ksim_engine* e, const PlanGroup& g, hipStream_t gs) {
-  ksim_random_go::RandGoArgs ga{e->d_reps, e->d_replist + g.first, e->d_go.p, e->N};
+  ksim_random_go::RandGoArgs ga{e->d_reps.p, e->d_replist.p + g.first, e->d_go.p, e->N};
   const bool in_lds = ksim_random_go::lds_bytes(e->N, true) <= 160 * 1024;
   const size_t lds = ksim_random_go::lds_bytes(e->N, in_lds);
   if (in_lds) {
@@ -4065,7 +4000,7 @@ static int overlap_queue(ksim_engine* e, const RunEnv& env, const RunPlan& plan,
   const int rc = e->d_done.ensure(2 + (size_t)g.count, &grew);
   if (rc) return rc;
   if (grew) KSIM_HIP(hipMemset(e->d_done.p, 0, sizeof(unsigned long long) * (2 + (size_t)g.count)));
-  if (!e->ev_ovl) KSIM_HIP(hipEventCreateWithFlags(&e->ev_ovl, hipEventDisableTiming));
+  if (int rc = e->ev_ovl.ensure(hipEventDisableTiming)) return rc;
   KSIM_HIP(hipMemsetAsync(e->d_done.p, 0, 2 * sizeof(unsigned long long), gs));  // tickets; entries keep epochs
   KSIM_HIP(hipEventRecord(e->ev_ovl, gs));
   *overlapped = true;
@@ -4084,7 +4019,7 @@ static int launch_scan1(ksim_engine* e, const RunEnv& env, const RunPlan& plan, 
   const void* f = !mix ? scan1_fn(g.kind, e->report, reg)
                   : e->report ? (reg ? (const void*)k_scan1_mix<true, true> : (const void*)k_scan1_mix<true, false>)
                               : (reg ? (const void*)k_scan1_mix<false, true> : (const void*)k_scan1_mix<false, false>);
-  Scan1Args sa{e->d_reps, e->d_replist + g.first, e->N, dead_skip(e, env, group_reps(plan, g)) ? 1 : 0, nullptr, 0};
+  Scan1Args sa{e->d_reps.p, e->d_replist.p + g.first, e->N, dead_skip(e, env, group_reps(plan, g)) ? 1 : 0, nullptr, 0};
   KSIM_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
   if (mix && plan.concurrent && e->report && gi > 0 && env.report_overlap) {
     const int rc = overlap_queue(e, env, plan, g, f, gs, sa, overlapped);
@@ -4101,15 +4036,8 @@ static int launch_scan1(ksim_engine* e, const RunEnv& env, const RunPlan& plan, 
 // carry the flags).  The next group is launched after that, so none of its workgroups holds a CU these wait for.
 static int launch_gated(ksim_engine* e, bool gate, int n, const char* what,
                         const std::function<int(int*, int, bool*)>& launch) {
-  if (gate && n > e->started_cap) {  // the host-mapped start flags, one per workgroup
-    if (e->h_started) KSIM_HIP(hipHostFree(e->h_started));
-    e->h_started = nullptr;
-    KSIM_HIP(hipHostMalloc((void**)&e->h_started, sizeof(int) * (size_t)n, hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(e->h_started, 0, sizeof(int) * (size_t)n);
-    KSIM_HIP(hipHostGetDevicePointer((void**)&e->d_started, e->h_started, 0));
-    e->started_cap = n;
-  }
-  int* flags = gate ? e->d_started : nullptr;
+  if (int rc = gate ? e->started.ensure((size_t)n) : KSIM_OK) return rc;  // the host-mapped start flags, one per workgroup
+  int* flags = gate ? e->started.d : nullptr;
   const int epoch = gate ? (e->gate_epoch = (e->gate_epoch % 0x3fffffff) + 1) : 0;  // the launch stores it into them
   bool gated = gate;
   const int rc = launch(flags, epoch, &gated);
@@ -4118,7 +4046,7 @@ static int launch_gated(ksim_engine* e, bool gate, int n, const char* what,
   // wait until the n workgroups have stored the epoch (bounded: past 2 s the gate gives up, counts it and says so on
   // stderr -- it orders work, it decides nothing)
   const auto t0 = std::chrono::steady_clock::now();
-  volatile int* fl = e->h_started;
+  volatile int* fl = e->started.h;
   if (e->last_gate == 0) e->last_gate = 1;
   for (int w = 0; w < n;) {
     if (fl[w] == epoch) { ++w; continue; }
@@ -4211,15 +4139,15 @@ static int launch_replay(ksim_engine* e, const RunEnv& env, const RunPlan& plan,
   ra.pm_c = e->last_pf_memo = replay_pf_memo(e, env, plan, g, K, S, &lds);
   ra.pm_ver0 = env.pf_memo_ver0 > 0 && env.pf_memo_ver0 < (long)ksim_replay::kPmInvalid ? (unsigned)env.pf_memo_ver0 : 0u;
   ra.pf_guess = env.pf_guess ? 1 : 0;
-  ra.reps = e->d_reps;
-  ra.rep_list = e->d_replist + g.first;
+  ra.reps = e->d_reps.p;
+  ra.rep_list = e->d_replist.p + g.first;
   ra.N = e->N;
   ra.K = K;
   ra.S = S;
-  ra.gran = e->d_gran;
+  ra.gran = e->d_gran.p;
   ra.hist = plan.any_delete ? e->d_hist.p : nullptr;
   ra.hist_stride = std::max(max_ev, 1);
-  ra.fail = e->d_fail;
+  ra.fail = e->d_fail.p;
   ra.prof = nullptr;
   ra.skip = dead_skip(e, env, group_reps(plan, g)) ? 1 : 0;
   if (profile) {
@@ -4230,10 +4158,10 @@ static int launch_replay(ksim_engine* e, const RunEnv& env, const RunPlan& plan,
   }
   // re-initialise every polled word before the launch (granule tags restart at step 1; K = 1 polls none)
   if (K > 1)
-    KSIM_HIP(hipMemsetAsync(e->d_gran, 0,
+    KSIM_HIP(hipMemsetAsync(e->d_gran.p, 0,
                             sizeof(unsigned long long) * (size_t)e->R * 2 * ksim_replay::kMaxK * ksim_replay::kGranW,
                             e->stream));
-  const TypDev* tp = e->d_tp;
+  const TypDev* tp = e->d_tp.p;
   rc = launch_persistent(replay_kernel(pol, K, general), Rg * K, ksim_replay::kRBlock, lds, gs, e->coop && K > 1, ra, tp);
   if (rc) return rc;
   note_launch(e, "k_replay", K, nullptr, Rg);
@@ -4248,10 +4176,10 @@ static int launch_replay(ksim_engine* e, const RunEnv& env, const RunPlan& plan,
 // ---- a concurrent run's side streams ----
 // Fork: the side streams start behind this point of the engine stream (KSIM_GROUP_TIMES=1: a timing event there too).
 static int fork_streams(ksim_engine* e, const RunEnv& env) {
-  if (!e->ev_fork) KSIM_HIP(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
+  if (int rc = e->ev_fork.ensure(hipEventDisableTiming)) return rc;
   KSIM_HIP(hipEventRecord(e->ev_fork, e->stream));
   if (env.group_times) {
-    if (!e->tev_fork) KSIM_HIP(hipEventCreate(&e->tev_fork));
+    if (int rc = e->tev_fork.ensure()) return rc;
     KSIM_HIP(hipEventRecord(e->tev_fork, e->stream));
   }
   return KSIM_OK;
@@ -4261,10 +4189,7 @@ static int fork_streams(ksim_engine* e, const RunEnv& env) {
 static int enter_side_stream(ksim_engine* e, const PlanGroup& g, unsigned* used) {
   const int i = g.side;
   if (i < 0) return KSIM_OK;
-  if (!e->side[i]) {
-    KSIM_HIP(hipStreamCreateWithFlags(&e->side[i], hipStreamNonBlocking));
-    KSIM_HIP(hipEventCreateWithFlags(&e->side_ev[i], hipEventDisableTiming));
-  }
+  if (e->side[i].ensure() || e->side_ev[i].ensure(hipEventDisableTiming)) return KSIM_EHIP;
   if (!(*used & (1u << i))) KSIM_HIP(hipStreamWaitEvent(e->side[i], e->ev_fork, 0));
   *used |= 1u << i;
   return KSIM_OK;
@@ -4274,10 +4199,10 @@ static int enter_side_stream(ksim_engine* e, const PlanGroup& g, unsigned* used)
 static int record_group_times(ksim_engine* e, const RunEnv& env, const RunPlan& plan, unsigned used) {
   e->tev_used = 0u;
   if (!plan.concurrent || !env.group_times) return KSIM_OK;
-  if (!e->tev_fork) KSIM_HIP(hipEventCreate(&e->tev_fork));
+  if (int rc = e->tev_fork.ensure()) return rc;
   for (int i = 0; i < (int)ksim_engine::kSide; ++i) {
     if (!(used & (1u << i))) continue;
-    if (!e->tev_side[i]) KSIM_HIP(hipEventCreate(&e->tev_side[i]));
+    if (int rc = e->tev_side[i].ensure()) return rc;
     KSIM_HIP(hipEventRecord(e->tev_side[i], e->side[i]));
   }
   e->tev_used = used;
@@ -4299,11 +4224,9 @@ static int join_streams(ksim_engine* e, unsigned used) {
 // none): the group whose replicas report one by one as each ends (overlap_queue), behind the first group on its stream.
 static int launch_group_reports(ksim_engine* e, const RunPlan& plan, int ovl_group) {
   const size_t ng = plan.groups.size();
-  if (e->grp_rev.size() < 2 * ng) {
-    const size_t had = e->grp_rev.size();
-    e->grp_rev.resize(2 * ng, nullptr);
-    for (size_t q = had; q < e->grp_rev.size(); ++q) KSIM_HIP(hipEventCreate(&e->grp_rev[q]));
-  }
+  if (e->grp_rev.size() < 2 * ng) e->grp_rev.resize(2 * ng);
+  for (DevEvent& v : e->grp_rev)
+    if (v.ensure()) return KSIM_EHIP;
   for (size_t gi = 0; gi < ng; ++gi) {
     const PlanGroup& g = plan.groups[gi];
     const bool ovl = (int)gi == ovl_group;
@@ -4314,11 +4237,11 @@ static int launch_group_reports(ksim_engine* e, const RunPlan& plan, int ovl_gro
     KSIM_HIP(hipEventRecord(e->grp_rev[2 * gi], rs));
     if (ovl) {
       hipLaunchKernelGGL(ksim_rep::k_report_overlap, dim3(std::min(g.count, std::max(1, e->cus - e->cus / 16))),
-                         dim3(ksim_rep::kScanBlock), 0, rs, (const ReplicaDev*)e->d_reps, (const TypDev*)e->d_tp, e->N,
-                         (const int*)(e->d_replist + g.first), g.count, e->d_done.p, e->done_epoch, e->d_fail);
+                         dim3(ksim_rep::kScanBlock), 0, rs, (const ReplicaDev*)e->d_reps.p, (const TypDev*)e->d_tp.p, e->N,
+                         (const int*)(e->d_replist.p + g.first), g.count, e->d_done.p, e->done_epoch, e->d_fail.p);
       KSIM_HIP(hipGetLastError());
     } else {
-      const int rc = run_report(e, mev, rs, e->d_replist + g.first, g.count);
+      const int rc = run_report(e, mev, rs, e->d_replist.p + g.first, g.count);
       if (rc) return rc;
     }
     KSIM_HIP(hipEventRecord(e->grp_rev[2 * gi + 1], rs));
@@ -4335,8 +4258,8 @@ static int run_persistent(ksim_engine* e, const RunEnv& env, int max_ev) {
   if (rc) return rc;
   e->last_memo = e->last_hmemo = e->last_rgo = e->last_scan1 = 0;
   e->last_launches = (int)plan.groups.size();
-  KSIM_HIP(hipMemcpyAsync(e->d_replist, plan.order.data(), sizeof(int) * plan.order.size(), hipMemcpyHostToDevice, e->stream));
-  KSIM_HIP(hipMemsetAsync(e->d_fail, 0, sizeof(int), e->stream));
+  KSIM_HIP(hipMemcpyAsync(e->d_replist.p, plan.order.data(), sizeof(int) * plan.order.size(), hipMemcpyHostToDevice, e->stream));
+  KSIM_HIP(hipMemsetAsync(e->d_fail.p, 0, sizeof(int), e->stream));
   if (plan.concurrent && (rc = fork_streams(e, env))) return rc;
   unsigned used = 0u;  // side streams the run has launched on
   int ovl_group = -1;
@@ -4365,7 +4288,7 @@ static int run_persistent(ksim_engine* e, const RunEnv& env, int max_ev) {
 static int run_graph(ksim_engine* e, int max_ev) {
   int rc = build_graph(e);
   if (rc) return rc;
-  KSIM_HIP(hipMemsetAsync(e->d_base, 0, sizeof(int), e->stream));
+  KSIM_HIP(hipMemsetAsync(e->d_base.p, 0, sizeof(int), e->stream));
   const int reps = (max_ev + e->K - 1) / e->K;
   for (int i = 0; i < reps; ++i) KSIM_HIP(hipGraphLaunch(e->graph, e->stream));
   return KSIM_OK;
@@ -4375,7 +4298,7 @@ int ksim_engine_run(ksim_engine* e) {
   if (!e) return KSIM_EINVAL;
   int max_ev = 0;
   for (int r = 0; r < e->R; ++r) {
-    if (!e->d_ev[r]) return KSIM_ESTATE;
+    if (!e->d_ev[r].p) return KSIM_ESTATE;
     max_ev = std::max(max_ev, e->n_events[r]);
   }
   KSIM_HIP(hipSetDevice(e->device));
@@ -4394,7 +4317,7 @@ int ksim_engine_run(ksim_engine* e) {
   KSIM_HIP(hipEventRecord(e->ev0, e->stream));
   rc = reset_state(e);
   if (rc) return rc;
-  if (e->report) KSIM_HIP(hipMemsetAsync(e->d_last, 0xff, sizeof(int32_t) * (size_t)e->N * e->R, e->stream));
+  if (e->report) KSIM_HIP(hipMemsetAsync(e->d_last.p, 0xff, sizeof(int32_t) * (size_t)e->N * e->R, e->stream));
   // run_mode 1: the per-pod path (k_step, + k_step_pwr for the PWR policies, hipGraph)
   const bool step_path = e->run_mode == 1;
   for (int r = 0; r < e->R; ++r)
@@ -4445,7 +4368,7 @@ int ksim_engine_run(ksim_engine* e) {
   e->last_step_path = step_path;
   if (!step_path && e->shard_world == 0) {
     int fail = 0;
-    KSIM_HIP(hipMemcpy(&fail, e->d_fail, sizeof(int), hipMemcpyDeviceToHost));
+    KSIM_HIP(hipMemcpy(&fail, e->d_fail.p, sizeof(int), hipMemcpyDeviceToHost));
     if (fail & 2) return KSIM_ERANGE;  // a raw PWR score outside the 24-bit key field
     if (fail & 60) std::fprintf(stderr, "ksim: a memoised kernel's LDS wait timed out (fail bits 0x%x)\n", fail);
     if (fail & 64) std::fprintf(stderr, "ksim: the overlapped report waited too long for a replay (fail bits 0x%x)\n", fail);
@@ -4483,15 +4406,16 @@ int ksim_engine_set_shard(ksim_engine* e, int rank, int world, int node_offset, 
       return KSIM_EHIP;
     }
   }
-  KSIM_HIP(hipMalloc(&e->d_send, 4 * sizeof(unsigned long long)));
-  KSIM_HIP(hipMalloc(&e->d_recv, 4 * sizeof(unsigned long long) * (size_t)world));
-  KSIM_HIP(hipMemset(e->d_send, 0, 4 * sizeof(unsigned long long)));
+  int rc = e->d_send.alloc(4);
+  if (!rc) rc = e->d_recv.alloc(4 * (size_t)world);
+  if (!rc) rc = e->d_send.zero(e->stream);
+  if (rc) return rc;
   e->shard_world = world;
   e->shard_rank = rank;
   e->node_off = node_offset;
   e->n_global = n_global;
   e->reps[0].node_off = node_offset;
-  int rc = upload_reps(e);
+  rc = upload_reps(e);
   if (rc) return rc;
   KSIM_HIP(hipStreamSynchronize(e->stream));
   return KSIM_OK;
@@ -4531,14 +4455,16 @@ int ksim_shard_peer_handle(ksim_engine* e, uint8_t* out) {
   if (!e || !out) return KSIM_EINVAL;
   if (e->shard_world < 1 || e->comm || e->xfn) return KSIM_ESTATE;
   KSIM_HIP(hipSetDevice(e->device));
-  if (!e->d_pgran) {
+  if (!e->d_pgran.p) {
     // uncached device memory: the peers' stores land in it over xGMI and the local polls read it there
-    KSIM_HIP(hipExtMallocWithFlags((void**)&e->d_pgran, kPeerGranBytes, hipDeviceMallocUncached));
-    KSIM_HIP(hipMemset(e->d_pgran, 0, kPeerGranBytes));
+    int rc = e->d_pgran.alloc(kPeerGranBytes / sizeof(unsigned long long), hipDeviceMallocUncached);
+    if (!rc) rc = e->d_pgran.zero(e->stream);
+    if (rc) return rc;
+    KSIM_HIP(hipStreamSynchronize(e->stream));
   }
   if (e->pgran_handle.empty()) {
     hipIpcMemHandle_t h;
-    KSIM_HIP(hipIpcGetMemHandle(&h, e->d_pgran));
+    KSIM_HIP(hipIpcGetMemHandle(&h, e->d_pgran.p));
     static_assert(sizeof(hipIpcMemHandle_t) + 20 <= KSIM_SHARD_HANDLE_BYTES, "IPC handle size");
     hipDeviceProp_t prop;
     KSIM_HIP(hipGetDeviceProperties(&prop, e->device));
@@ -4554,7 +4480,7 @@ int ksim_shard_peer_handle(ksim_engine* e, uint8_t* out) {
 
 int ksim_engine_set_shard_peers(ksim_engine* e, const uint8_t* handles) {
   if (!e || !handles) return KSIM_EINVAL;
-  if (e->shard_world < 1 || !e->d_pgran || e->pgran_handle.empty() || !e->peers.empty()) return KSIM_ESTATE;
+  if (e->shard_world < 1 || !e->d_pgran.p || e->pgran_handle.empty() || !e->peers.empty()) return KSIM_ESTATE;
   KSIM_HIP(hipSetDevice(e->device));
   const int world = e->shard_world;
   if (const long ep = test_knob("peer_epoch0", 0))  // tests: start the run epoch near its wrap
@@ -4589,7 +4515,7 @@ int ksim_engine_set_shard_peers(ksim_engine* e, const uint8_t* handles) {
   }
   for (int q = 0; q < world; ++q) {
     if (q == e->shard_rank) {
-      e->peers[q] = e->d_pgran;
+      e->peers[q] = e->d_pgran.p;
       continue;
     }
     hipIpcMemHandle_t h;
@@ -4630,20 +4556,20 @@ static int run_hmemo_peer(ksim_engine* e, const RunEnv& env, int max_ev) {
   const int stride = std::max(max_ev, 1);
   hipStream_t st = e->stream;
   const int zero = 0;
-  KSIM_HIP(hipMemcpyAsync(e->d_replist, &zero, sizeof(int), hipMemcpyHostToDevice, st));
+  KSIM_HIP(hipMemcpyAsync(e->d_replist.p, &zero, sizeof(int), hipMemcpyHostToDevice, st));
   int rc = prepare_hmemo(e, std::vector<int>{0}, max_ev, K, S);
   if (rc) return rc;
   if (!e->hplan_ok) return KSIM_ENOTSUP;
   e->mplan_dirty = true;
-  KSIM_HIP(hipMemcpyAsync(e->d_nodes, e->d_nodes_init, sizeof(NodeRec) * (size_t)e->N, hipMemcpyDeviceToDevice, st));
-  KSIM_HIP(hipMemcpyAsync(e->d_tags, e->d_tags_init, sizeof(uint16_t) * e->tags_stride, hipMemcpyDeviceToDevice, st));
-  KSIM_HIP(hipMemsetAsync(e->d_res[0], 0xff, sizeof(ResultDev) * (size_t)stride, st));
+  KSIM_HIP(hipMemcpyAsync(e->d_nodes.p, e->d_nodes_init.p, sizeof(NodeRec) * (size_t)e->N, hipMemcpyDeviceToDevice, st));
+  KSIM_HIP(hipMemcpyAsync(e->d_tags.p, e->d_tags_init.p, sizeof(uint16_t) * e->tags_stride, hipMemcpyDeviceToDevice, st));
+  KSIM_HIP(hipMemsetAsync(e->d_res[0].p, 0xff, sizeof(ResultDev) * (size_t)stride, st));
   if ((rc = hmemo_init_keys(e, 1, 0, st, e->node_off))) return rc;
   HMemoArgs a = hmemo_args(e, env, 0, stride);
   a.roff = e->node_off;
   a.wbase = e->shard_rank * K;
   a.Ktot = Kt;
-  a.gran = e->d_pgran;
+  a.gran = e->d_pgran.p;
   a.npeer = world;
   e->peer_epoch = (e->peer_epoch + 1) & 0xffffff;  // every rank runs the same runs: the same epoch (24 bits)
   if (e->peer_epoch == 0) e->peer_epoch = 1;
@@ -4653,13 +4579,13 @@ static int run_hmemo_peer(ksim_engine* e, const RunEnv& env, int max_ev) {
     if ((rc = e->d_h_hist.ensure((size_t)K * stride))) return rc;
     a.hist = e->d_h_hist.p;
   }
-  KSIM_HIP(hipMemsetAsync(e->d_fail, 0, sizeof(int), st));
+  KSIM_HIP(hipMemsetAsync(e->d_fail.p, 0, sizeof(int), st));
   const bool gen = a.delay != 0;
   const void* f = Kt <= 64 ? (gen ? (const void*)k_hmemo<1, true> : (const void*)k_hmemo<1, false>)
                            : (gen ? (const void*)k_hmemo<4, true> : (const void*)k_hmemo<4, false>);
   if (K > resident_cap(e, f, e->hplan->lds)) return KSIM_ERANGE;
   KSIM_HIP(hipEventRecord(e->ev0, st));
-  const TypDev* tpp = e->d_tp;
+  const TypDev* tpp = e->d_tp.p;
   // a plain launch: K <= 64 one-per-CU workgroups are resident (checked above), and a cooperative launch
   // takes the device's one global-wave-sync resource, which a second shard process on the same device
   // would wait for behind the first's persistent kernel
@@ -4667,7 +4593,7 @@ static int run_hmemo_peer(ksim_engine* e, const RunEnv& env, int max_ev) {
   KSIM_HIP(hipEventRecord(e->ev1, st));
   KSIM_HIP(hipStreamSynchronize(st));
   int fail = 0;
-  KSIM_HIP(hipMemcpy(&fail, e->d_fail, sizeof(int), hipMemcpyDeviceToHost));
+  KSIM_HIP(hipMemcpy(&fail, e->d_fail.p, sizeof(int), hipMemcpyDeviceToHost));
   if (fail) return KSIM_ESTATE;
   float ms = 0;
   KSIM_HIP(hipEventElapsedTime(&ms, e->ev0, e->ev1));
@@ -4735,49 +4661,49 @@ static int run_replay_group(ksim_engine* const* engines, int world, const RunEnv
   hipStream_t st = e0->stream;
   KSIM_HIP(hipSetDevice(e0->device));
   int rc;
-  if (!e0->d_rgran) KSIM_HIP(hipMalloc(&e0->d_rgran, sizeof(unsigned long long) * 2 * 256 * kGranW));
-  if (!e0->d_rgreps) KSIM_HIP(hipMalloc(&e0->d_rgreps, sizeof(ReplicaDev) * 16));
-  if (!e0->d_rglist) {
-    KSIM_HIP(hipMalloc(&e0->d_rglist, sizeof(int) * 16));
+  if ((rc = e0->d_rgran.ensure((size_t)2 * 256 * kGranW))) return rc;
+  if ((rc = e0->d_rgreps.ensure(16))) return rc;
+  if (!e0->d_rglist.p) {
     std::vector<int> id(16);
     std::iota(id.begin(), id.end(), 0);
-    KSIM_HIP(hipMemcpy(e0->d_rglist, id.data(), sizeof(int) * 16, hipMemcpyHostToDevice));
+    if ((rc = e0->d_rglist.upload(id, st))) return rc;
+    KSIM_HIP(hipStreamSynchronize(st));  // `id` is pageable
   }
   bool skip = true;
   for (int k = 0; k < world; ++k) {
     ksim_engine* e = engines[k];
     KSIM_HIP(hipStreamSynchronize(e->stream));
-    KSIM_HIP(hipMemcpyAsync(e->d_nodes, e->d_nodes_init, sizeof(NodeRec) * (size_t)e->N, hipMemcpyDeviceToDevice, st));
-    KSIM_HIP(hipMemcpyAsync(e->d_tags, e->d_tags_init, sizeof(uint16_t) * e->tags_stride, hipMemcpyDeviceToDevice, st));
-    KSIM_HIP(hipMemsetAsync(e->d_res[0], 0xff, sizeof(ResultDev) * (size_t)std::max(e->n_events[0], 1), st));
-    KSIM_HIP(hipMemcpyAsync(e0->d_rgreps + k, e->d_reps, sizeof(ReplicaDev), hipMemcpyDeviceToDevice, st));
+    KSIM_HIP(hipMemcpyAsync(e->d_nodes.p, e->d_nodes_init.p, sizeof(NodeRec) * (size_t)e->N, hipMemcpyDeviceToDevice, st));
+    KSIM_HIP(hipMemcpyAsync(e->d_tags.p, e->d_tags_init.p, sizeof(uint16_t) * e->tags_stride, hipMemcpyDeviceToDevice, st));
+    KSIM_HIP(hipMemsetAsync(e->d_res[0].p, 0xff, sizeof(ResultDev) * (size_t)std::max(e->n_events[0], 1), st));
+    KSIM_HIP(hipMemcpyAsync(e0->d_rgreps.p + k, e->d_reps.p, sizeof(ReplicaDev), hipMemcpyDeviceToDevice, st));
     skip = skip && dead_skip(e, env, std::vector<int>{0});
   }
   ReplayArgs ra;
   std::memset(&ra, 0, sizeof ra);
-  ra.reps = e0->d_rgreps;
-  ra.rep_list = e0->d_rglist;
+  ra.reps = e0->d_rgreps.p;
+  ra.rep_list = e0->d_rglist.p;
   ra.N = N;
   ra.K = K;
   ra.S = S;
-  ra.gran = e0->d_rgran;
+  ra.gran = e0->d_rgran.p;
   ra.hist = nullptr;
   ra.hist_stride = std::max(max_ev, 1);
-  ra.fail = e0->d_fail;
+  ra.fail = e0->d_fail.p;
   ra.prof = nullptr;
   ra.skip = skip ? 1 : 0;
   ra.pf_guess = 1;
   ra.xK = Kt;
   ra.group = 1;
-  KSIM_HIP(hipMemsetAsync(e0->d_rgran, 0, sizeof(unsigned long long) * 2 * (size_t)Kt * kGranW, st));
-  KSIM_HIP(hipMemsetAsync(e0->d_fail, 0, sizeof(int), st));
+  KSIM_HIP(hipMemsetAsync(e0->d_rgran.p, 0, sizeof(unsigned long long) * 2 * (size_t)Kt * kGranW, st));
+  KSIM_HIP(hipMemsetAsync(e0->d_fail.p, 0, sizeof(int), st));
   KSIM_HIP(hipEventRecord(e0->ev0, st));
-  const TypDev* tp = e0->d_tp;  // (the cheap policies read no typical table)
+  const TypDev* tp = e0->d_tp.p;  // (the cheap policies read no typical table)
   if ((rc = launch_persistent(f, Kt, kRBlock, lds, st, e0->coop, ra, tp))) return rc;
   KSIM_HIP(hipEventRecord(e0->ev1, st));
   KSIM_HIP(hipStreamSynchronize(st));
   int fail = 0;
-  KSIM_HIP(hipMemcpy(&fail, e0->d_fail, sizeof(int), hipMemcpyDeviceToHost));
+  KSIM_HIP(hipMemcpy(&fail, e0->d_fail.p, sizeof(int), hipMemcpyDeviceToHost));
   if (fail) return KSIM_ESTATE;
   float ms = 0;
   KSIM_HIP(hipEventElapsedTime(&ms, e0->ev0, e0->ev1));
@@ -4810,7 +4736,7 @@ static int run_hmemo_group(ksim_engine* const* engines, int world, const RunEnv&
   for (int k = 0; k < world; ++k) {
     ksim_engine* e = engines[k];
     const int zero = 0;
-    KSIM_HIP(hipMemcpyAsync(e->d_replist, &zero, sizeof(int), hipMemcpyHostToDevice, e->stream));
+    KSIM_HIP(hipMemcpyAsync(e->d_replist.p, &zero, sizeof(int), hipMemcpyHostToDevice, e->stream));
     int rc = prepare_hmemo(e, std::vector<int>{0}, max_ev, K, S);
     if (rc) return rc;
     if (!e->hplan_ok) return KSIM_OK;
@@ -4823,22 +4749,23 @@ static int run_hmemo_group(ksim_engine* const* engines, int world, const RunEnv&
   if (Kt > resident_cap(e0, f, lds)) return KSIM_OK;
   hipStream_t st = e0->stream;
   KSIM_HIP(hipSetDevice(e0->device));
-  if (!e0->d_ggran) KSIM_HIP(hipMalloc(&e0->d_ggran, sizeof(unsigned long long) * 2 * 256 * 2));
-  if (!e0->d_hgargs) KSIM_HIP(hipMalloc(&e0->d_hgargs, sizeof(HMemoArgs) * 16));
+  int rc;
+  if ((rc = e0->d_ggran.ensure((size_t)2 * 256 * 2))) return rc;
+  if ((rc = e0->d_hgargs.ensure(16))) return rc;
   for (int k = 0; k < world; ++k) {
     ksim_engine* e = engines[k];
     KSIM_HIP(hipStreamSynchronize(e->stream));
-    KSIM_HIP(hipMemcpyAsync(e->d_nodes, e->d_nodes_init, sizeof(NodeRec) * (size_t)e->N, hipMemcpyDeviceToDevice, st));
-    KSIM_HIP(hipMemcpyAsync(e->d_tags, e->d_tags_init, sizeof(uint16_t) * e->tags_stride, hipMemcpyDeviceToDevice, st));
-    KSIM_HIP(hipMemsetAsync(e->d_res[0], 0xff, sizeof(ResultDev) * (size_t)std::max(e->n_events[0], 1), st));
-    int rc = hmemo_init_keys(e, 1, 0, st, e->node_off);
+    KSIM_HIP(hipMemcpyAsync(e->d_nodes.p, e->d_nodes_init.p, sizeof(NodeRec) * (size_t)e->N, hipMemcpyDeviceToDevice, st));
+    KSIM_HIP(hipMemcpyAsync(e->d_tags.p, e->d_tags_init.p, sizeof(uint16_t) * e->tags_stride, hipMemcpyDeviceToDevice, st));
+    KSIM_HIP(hipMemsetAsync(e->d_res[0].p, 0xff, sizeof(ResultDev) * (size_t)std::max(e->n_events[0], 1), st));
+    rc = hmemo_init_keys(e, 1, 0, st, e->node_off);
     if (rc) return rc;
     HMemoArgs a = hmemo_args(e, env, 0, stride);
     a.roff = e->node_off;
     a.wbase = k * K;
     a.Ktot = Kt;
-    a.gran = e0->d_ggran;
-    a.fail = e0->d_fail;
+    a.gran = e0->d_ggran.p;
+    a.fail = e0->d_fail.p;
     if (e->has_delete[0]) {
       rc = e->d_h_hist.ensure((size_t)K * stride);
       if (rc) return rc;
@@ -4846,13 +4773,13 @@ static int run_hmemo_group(ksim_engine* const* engines, int world, const RunEnv&
     }
     args[k] = a;
   }
-  KSIM_HIP(hipMemcpyAsync(e0->d_hgargs, args.data(), sizeof(HMemoArgs) * world, hipMemcpyHostToDevice, st));
-  KSIM_HIP(hipMemsetAsync(e0->d_ggran, 0, sizeof(unsigned long long) * 2 * (size_t)Kt * 2, st));
-  KSIM_HIP(hipMemsetAsync(e0->d_fail, 0, sizeof(int), st));
+  KSIM_HIP(hipMemcpyAsync(e0->d_hgargs.p, args.data(), sizeof(HMemoArgs) * world, hipMemcpyHostToDevice, st));
+  KSIM_HIP(hipMemsetAsync(e0->d_ggran.p, 0, sizeof(unsigned long long) * 2 * (size_t)Kt * 2, st));
+  KSIM_HIP(hipMemsetAsync(e0->d_fail.p, 0, sizeof(int), st));
   KSIM_HIP(hipStreamSynchronize(st));  // `args` is pageable
   KSIM_HIP(hipEventRecord(e0->ev0, st));
   KSIM_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const HMemoArgs* ap = reinterpret_cast<const HMemoArgs*>(e0->d_hgargs);
+  const HMemoArgs* ap = e0->d_hgargs.p;
   int Kk = K;
   void* params[] = {(void*)&ap, (void*)&Kk};
   const hipError_t lr = e0->coop ? hipLaunchCooperativeKernel(f, dim3(Kt), dim3(kHBlock), params, (unsigned)lds, st)
@@ -4865,7 +4792,7 @@ static int run_hmemo_group(ksim_engine* const* engines, int world, const RunEnv&
   KSIM_HIP(hipEventRecord(e0->ev1, st));
   KSIM_HIP(hipStreamSynchronize(st));
   int fail = 0;
-  KSIM_HIP(hipMemcpy(&fail, e0->d_fail, sizeof(int), hipMemcpyDeviceToHost));
+  KSIM_HIP(hipMemcpy(&fail, e0->d_fail.p, sizeof(int), hipMemcpyDeviceToHost));
   if (fail) return KSIM_ESTATE;
   float ms = 0;
   KSIM_HIP(hipEventElapsedTime(&ms, e0->ev0, e0->ev1));
@@ -4886,7 +4813,7 @@ int ksim_shard_group_run(ksim_engine* const* engines, int world) {
   for (int k = 0; k < world; ++k) {
     ksim_engine* e = engines[k];
     if (!e || e->shard_world != world || e->shard_rank != k || e->comm || e->xfn || e->device != e0->device ||
-        !e->d_ev[0])
+        !e->d_ev[0].p)
       return KSIM_EINVAL;
     if (e->n_events[0] != e0->n_events[0]) return KSIM_EINVAL;  // every shard sees the same events
     max_ev = std::max(max_ev, e->n_events[0]);
@@ -4906,28 +4833,28 @@ int ksim_shard_group_run(ksim_engine* const* engines, int world) {
     if (rc || done) return rc;
   }
   for (int k = 0; k < world; ++k) engines[k]->last_kernels = "k_step";
-  if (!e0->d_ptrs) KSIM_HIP(hipMalloc(&e0->d_ptrs, sizeof(unsigned long long*) * 32));
+  if (int rc = e0->d_ptrs.ensure(32)) return rc;
   std::vector<unsigned long long*> ptrs(32, nullptr);
   for (int k = 0; k < world; ++k) {
-    ptrs[k] = engines[k]->d_send;
-    ptrs[16 + k] = engines[k]->d_recv;
+    ptrs[k] = engines[k]->d_send.p;
+    ptrs[16 + k] = engines[k]->d_recv.p;
   }
   hipStream_t st = e0->stream;
-  KSIM_HIP(hipMemcpyAsync(e0->d_ptrs, ptrs.data(), sizeof(unsigned long long*) * 32, hipMemcpyHostToDevice, st));
+  KSIM_HIP(hipMemcpyAsync(e0->d_ptrs.p, ptrs.data(), sizeof(unsigned long long*) * 32, hipMemcpyHostToDevice, st));
   for (int k = 0; k < world; ++k) {
     ksim_engine* e = engines[k];
     KSIM_HIP(hipStreamSynchronize(e->stream));
-    KSIM_HIP(hipMemcpyAsync(e->d_nodes, e->d_nodes_init, sizeof(NodeRec) * (size_t)e->N, hipMemcpyDeviceToDevice, st));
-    KSIM_HIP(hipMemcpyAsync(e->d_tags, e->d_tags_init, sizeof(uint16_t) * e->tags_stride, hipMemcpyDeviceToDevice, st));
-    if (e->report) KSIM_HIP(hipMemsetAsync(e->d_last, 0xff, sizeof(int32_t) * (size_t)e->N, st));
+    KSIM_HIP(hipMemcpyAsync(e->d_nodes.p, e->d_nodes_init.p, sizeof(NodeRec) * (size_t)e->N, hipMemcpyDeviceToDevice, st));
+    KSIM_HIP(hipMemcpyAsync(e->d_tags.p, e->d_tags_init.p, sizeof(uint16_t) * e->tags_stride, hipMemcpyDeviceToDevice, st));
+    if (e->report) KSIM_HIP(hipMemsetAsync(e->d_last.p, 0xff, sizeof(int32_t) * (size_t)e->N, st));
   }
   KSIM_HIP(hipEventRecord(e0->ev0, st));
   int rc;
   for (int s = 0; s < max_ev; ++s) {
     for (int k = 0; k < world; ++k)
       if ((rc = shard_local(engines[k], st, nullptr, s))) return rc;
-    hipLaunchKernelGGL(k_shard_gather, dim3(1), dim3(1024), 0, st, (unsigned long long* const*)e0->d_ptrs,
-                       (unsigned long long* const*)(e0->d_ptrs + 16), world);
+    hipLaunchKernelGGL(k_shard_gather, dim3(1), dim3(1024), 0, st, (unsigned long long* const*)e0->d_ptrs.p,
+                       (unsigned long long* const*)(e0->d_ptrs.p + 16), world);
     KSIM_HIP(hipGetLastError());
     for (int k = 0; k < world; ++k)
       if ((rc = shard_commit(engines[k], st, nullptr, s))) return rc;
@@ -4961,11 +4888,11 @@ int ksim_engine_set_report(ksim_engine* e, int enable) {
 
 int ksim_engine_get_reports(ksim_engine* e, int replica, ksim_report* out, int n) {
   if (!e || !out || replica < 0 || replica >= e->R || n < 0 || n > e->n_events[replica]) return KSIM_EINVAL;
-  if (!e->report || !e->d_rep[replica]) return KSIM_ESTATE;
+  if (!e->report || !e->d_rep[replica].p) return KSIM_ESTATE;
   if (n == 0) return KSIM_OK;
   std::vector<RepAcc> h((size_t)n);
   KSIM_HIP(hipSetDevice(e->device));
-  KSIM_HIP(hipMemcpyAsync(h.data(), e->d_rep[replica], sizeof(RepAcc) * n, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipMemcpyAsync(h.data(), e->d_rep[replica].p, sizeof(RepAcc) * n, hipMemcpyDeviceToHost, e->stream));
   KSIM_HIP(hipStreamSynchronize(e->stream));
   for (int i = 0; i < n; ++i) {
     ksim_report& o = out[i];
@@ -4985,11 +4912,11 @@ int ksim_engine_get_reports(ksim_engine* e, int replica, ksim_report* out, int n
 
 int ksim_engine_get_power_reports(ksim_engine* e, int replica, ksim_power_report* out, int n) {
   if (!e || !out || replica < 0 || replica >= e->R || n < 0 || n > e->n_events[replica]) return KSIM_EINVAL;
-  if (!e->report || !e->d_rep[replica] || !e->pw_set[replica]) return KSIM_ESTATE;
+  if (!e->report || !e->d_rep[replica].p || !e->pw_set[replica]) return KSIM_ESTATE;
   if (n == 0) return KSIM_OK;
   std::vector<RepAcc> h((size_t)n);
   KSIM_HIP(hipSetDevice(e->device));
-  KSIM_HIP(hipMemcpyAsync(h.data(), e->d_rep[replica], sizeof(RepAcc) * n, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipMemcpyAsync(h.data(), e->d_rep[replica].p, sizeof(RepAcc) * n, hipMemcpyDeviceToHost, e->stream));
   KSIM_HIP(hipStreamSynchronize(e->stream));
   for (int i = 0; i < n; ++i) {
     ksim_power_report& o = out[i];
@@ -5056,8 +4983,9 @@ int ksim_engine_last_run_path(ksim_engine* e, int* path) {
 int ksim_engine_time_steps(ksim_engine* e, int n_steps, double* mean_kernel_us) {
   if (!e || !mean_kernel_us || n_steps <= 0) return KSIM_EINVAL;
   KSIM_HIP(hipSetDevice(e->device));
-  std::vector<hipEvent_t> evs(2 * n_steps);
-  for (auto& x : evs) KSIM_HIP(hipEventCreate(&x));
+  std::vector<DevEvent> evs(2 * n_steps);
+  for (DevEvent& x : evs)
+    if (x.ensure()) return KSIM_EHIP;
   int rc = reset_state(e);
   if (rc) return rc;
   StepArgs a = base_args(e);
@@ -5066,7 +4994,7 @@ int ksim_engine_time_steps(ksim_engine* e, int n_steps, double* mean_kernel_us) 
   for (int i = 0; i < n_steps; ++i) {
     a.step_off = i;
     KSIM_HIP(hipEventRecord(evs[2 * i], e->stream));
-    hipLaunchKernelGGL(k_step, dim3(e->bpr * e->R), dim3(kBlock), 0, e->stream, a, (const TypDev*)e->d_tp);
+    hipLaunchKernelGGL(k_step, dim3(e->bpr * e->R), dim3(kBlock), 0, e->stream, a, (const TypDev*)e->d_tp.p);
     if (any_pwr(e)) hipLaunchKernelGGL(k_step_pwr, dim3(e->bpr * e->R), dim3(kBlock), 0, e->stream, a);
     KSIM_HIP(hipEventRecord(evs[2 * i + 1], e->stream));
   }
@@ -5077,7 +5005,6 @@ int ksim_engine_time_steps(ksim_engine* e, int n_steps, double* mean_kernel_us) 
     KSIM_HIP(hipEventElapsedTime(&ms, evs[2 * i], evs[2 * i + 1]));
     tot += ms;
   }
-  for (auto& x : evs) (void)hipEventDestroy(x);
   *mean_kernel_us = tot * 1000.0 / n_steps;
   return KSIM_OK;
 }
@@ -5098,7 +5025,7 @@ int ksim_engine_get_results(ksim_engine* e, int replica, ksim_result* out, int n
   if (!e || !out || replica < 0 || replica >= e->R || n < 0 || n > e->n_events[replica]) return KSIM_EINVAL;
   if (n == 0) return KSIM_OK;
   KSIM_HIP(hipSetDevice(e->device));
-  KSIM_HIP(hipMemcpyAsync(out, e->d_res[replica], sizeof(ResultDev) * n, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipMemcpyAsync(out, e->d_res[replica].p, sizeof(ResultDev) * n, hipMemcpyDeviceToHost, e->stream));
   KSIM_HIP(hipStreamSynchronize(e->stream));
   return KSIM_OK;
 }
@@ -5109,7 +5036,7 @@ int ksim_engine_get_nodes(ksim_engine* e, int replica, ksim_node* out) {
   std::vector<NodeRec> h(e->N);
   std::vector<uint16_t> tags(e->tags_stride);
   KSIM_HIP(hipMemcpyAsync(h.data(), e->reps[replica].nodes, sizeof(NodeRec) * e->N, hipMemcpyDeviceToHost, e->stream));
-  KSIM_HIP(hipMemcpyAsync(tags.data(), e->d_tags + (size_t)replica * e->tags_stride, sizeof(uint16_t) * e->tags_stride,
+  KSIM_HIP(hipMemcpyAsync(tags.data(), e->d_tags.p + (size_t)replica * e->tags_stride, sizeof(uint16_t) * e->tags_stride,
                           hipMemcpyDeviceToHost, e->stream));
   KSIM_HIP(hipStreamSynchronize(e->stream));
   if (e->h_nodes[replica].size() != (size_t)e->N) return KSIM_ESTATE;
@@ -5155,10 +5082,9 @@ int ksim_engine_deschedule(ksim_engine* e, int policy, double ratio) {
   const bool in_lds = tab <= (size_t)ksim_ds::kSelLdsBytes;
   if (!rc && !in_lds) rc = e->d_ds_tab.ensure(ksim_ds::sel_tab_stride(e->N) * R);
   if (rc) return rc;
-  if (!e->ev_ds0) KSIM_HIP(hipEventCreate(&e->ev_ds0));
-  if (!e->ev_ds1) KSIM_HIP(hipEventCreate(&e->ev_ds1));
+  if (e->ev_ds0.ensure() || e->ev_ds1.ensure()) return KSIM_EHIP;
   ksim_ds::DsArgs a;
-  a.reps = e->d_reps;
+  a.reps = e->d_reps.p;
   a.eoff = e->d_ds_eoff.p;
   a.eval = e->d_ds_eval.p;
   a.gone = e->d_ds_gone.p;
@@ -5177,7 +5103,7 @@ int ksim_engine_deschedule(ksim_engine* e, int policy, double ratio) {
     const dim3 grid((unsigned)((max_ev + ksim_ds::kEvalBlock - 1) / ksim_ds::kEvalBlock), (unsigned)R);
     hipLaunchKernelGGL(ksim_ds::k_desched_mark, grid, dim3(ksim_ds::kEvalBlock), 0, e->stream, a);
     KSIM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ksim_ds::k_desched_eval, grid, dim3(ksim_ds::kEvalBlock), 0, e->stream, a, (const TypDev*)e->d_tp);
+    hipLaunchKernelGGL(ksim_ds::k_desched_eval, grid, dim3(ksim_ds::kEvalBlock), 0, e->stream, a, (const TypDev*)e->d_tp.p);
     KSIM_HIP(hipGetLastError());
   }
   std::vector<int32_t> bound((size_t)R, 0);

@@ -1,37 +1,52 @@
-// Host-side plumbing of the engine that knows nothing of the engine itself: the growable device buffer and the
-// environment knobs.  Host code only.  Included by ksim_engine.hip below KSIM_HIP; DevBuf calls hipMalloc / hipFree /
-// hipMemcpyAsync as the includer declares them (a host check of its grow / upload / release logic supplies
-// malloc-backed ones).
+// Host-side plumbing of the engine that knows nothing of the engine itself: the owning handles of its device
+// resources and the environment knobs.  Host code only.  Included by ksim_engine.hip below KSIM_HIP; the handles call
+// the HIP functions as the includer declares them (tests/native_host supplies malloc-backed ones and checks the
+// grow / upload / move / release logic on the CPU).  Every handle frees what it holds in its destructor, on the
+// device that is current then: the owner sets it first.
 #pragma once
 
 #include <algorithm>
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 #include <vector>
 
-// A device buffer that grows on demand: the pointer and its capacity in one owning object.
+// A device buffer: the pointer and its capacity in one owning, movable object.
 template <typename T>
 struct DevBuf {
   T* p = nullptr;   // kernels take it by name: args.keys = e->d_h_keys.p
-  size_t cap = 0;   // elements asked for by the ensure() that allocated p
+  size_t cap = 0;   // elements asked for by the alloc() / ensure() that allocated p
 
   DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;  // one owner: the engine
-  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}  // one owner: no copies
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = std::exchange(o.p, nullptr);
+      cap = std::exchange(o.cap, 0);
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
+
+  // Exactly n elements (one when n is 0), allocated afresh: what was held is freed first, and on failure the
+  // buffer is left empty.  ext_flags: hipExtMallocWithFlags flags (hipDeviceMallocUncached), 0 for a plain hipMalloc.
+  int alloc(size_t n, unsigned ext_flags = 0) {
+    release();
+    const size_t bytes = sizeof(T) * std::max(n, (size_t)1);
+    KSIM_HIP(ext_flags ? hipExtMallocWithFlags((void**)&p, bytes, ext_flags) : hipMalloc((void**)&p, bytes));
+    cap = n;
+    return KSIM_OK;
+  }
 
   // Room for n elements.  Reallocates when n exceeds the capacity or nothing is allocated yet; the old
   // contents are then gone (*grew, if given, says so: a caller whose contents carry state re-initialises them).
   int ensure(size_t n, bool* grew = nullptr) {
-    if (grew) *grew = false;
-    if (n <= cap && p) return KSIM_OK;
-    if (p) KSIM_HIP(hipFree(p));
-    p = nullptr;
-    cap = 0;
-    KSIM_HIP(hipMalloc(&p, sizeof(T) * std::max(n, (size_t)1)));
-    cap = n;
-    if (grew) *grew = true;
-    return KSIM_OK;
+    const bool grow = n > cap || !p;
+    const int rc = grow ? alloc(n) : KSIM_OK;
+    if (grew) *grew = grow && !rc;
+    return rc;
   }
 
   // ensure(v.size()), then v copied in on stream st (v is pageable: the caller synchronises before v goes away).
@@ -42,6 +57,12 @@ struct DevBuf {
     return KSIM_OK;
   }
 
+  int fill(int byte, hipStream_t st) {  // every byte of the cap elements, on stream st
+    if (cap) KSIM_HIP(hipMemsetAsync(p, byte, sizeof(T) * cap, st));
+    return KSIM_OK;
+  }
+  int zero(hipStream_t st) { return fill(0, st); }
+
   void release() {
     if (p) (void)hipFree(p);
     p = nullptr;
@@ -49,12 +70,63 @@ struct DevBuf {
   }
 };
 
-// Plain device pointers and DevBufs freed through one list, in the order given (ksim_engine_destroy).
-static inline void release_one(void* p) { (void)hipFree(p); }
-template <typename T>
-static void release_one(DevBuf<T>& b) { b.release(); }
-template <typename... B>
-static void release_all(B&... b) { (release_one(b), ...); }
+// An owned HIP object (event, stream, instantiated graph): movable, reads as the handle it holds; reset() destroys
+// what is held and takes another.  Destroying a stream does not wait for its work: the owner drains it first.
+template <typename H, hipError_t (*Destroy)(H)>
+struct DevHandle {
+  H h = nullptr;
+
+  DevHandle() = default;
+  DevHandle(DevHandle&& o) noexcept : h(std::exchange(o.h, nullptr)) {}  // one owner: no copies
+  ~DevHandle() { reset(); }
+  operator H() const { return h; }
+  void reset(H next = nullptr) {
+    if (h) (void)Destroy(h);
+    h = next;
+  }
+};
+using GraphExec = DevHandle<hipGraphExec_t, hipGraphExecDestroy>;
+
+// Created on first use: an event (hipEventDefault: a timing event, as hipEventCreate makes) and a non-blocking stream.
+struct DevEvent : DevHandle<hipEvent_t, hipEventDestroy> {
+  int ensure(unsigned flags = hipEventDefault) {
+    if (!h) KSIM_HIP(hipEventCreateWithFlags(&h, flags));
+    return KSIM_OK;
+  }
+};
+struct DevStream : DevHandle<hipStream_t, hipStreamDestroy> {
+  int ensure() {
+    if (!h) KSIM_HIP(hipStreamCreateWithFlags(&h, hipStreamNonBlocking));
+    return KSIM_OK;
+  }
+};
+
+// Host-mapped coherent int flags the device stores and the host polls: host pointer, device address, capacity.
+struct MappedFlags {
+  int* h = nullptr;
+  int* d = nullptr;
+  size_t cap = 0;
+
+  MappedFlags() = default;
+  MappedFlags(const MappedFlags&) = delete;
+  MappedFlags& operator=(const MappedFlags&) = delete;
+  ~MappedFlags() { release(); }
+
+  int ensure(size_t n) {  // room for n flags; a larger block replaces the old one (freed first) and starts zeroed
+    if (n <= cap && h) return KSIM_OK;
+    release();
+    KSIM_HIP(hipHostMalloc((void**)&h, sizeof(int) * std::max(n, (size_t)1), hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(h, 0, sizeof(int) * n);
+    if (hipHostGetDevicePointer((void**)&d, h, 0) != hipSuccess) return release(), KSIM_EHIP;
+    cap = n;
+    return KSIM_OK;
+  }
+  void release() {
+    if (h) (void)hipHostFree(h);
+    h = d = nullptr;
+    cap = 0;
+  }
+};
 
 // Environment knobs.  Besides the five plain ones (KSIM_PROFILE, KSIM_COOP, KSIM_CUS,
 // KSIM_SIDE_STREAMS, KSIM_GROUP_TIMES), two comma-separated key=value lists: KSIM_VARIANT selects the measured
