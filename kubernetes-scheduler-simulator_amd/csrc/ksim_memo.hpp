@@ -273,8 +273,10 @@ __device__ __forceinline__ unsigned memo_key_scalar(const NodeV& n, const PodDev
 
 // F = NodeGpuShareFragAmountScore of one state (frag.go:148-203, 411-418, 460-493) by ONE wave:
 // lane t classifies typical pod t (64 per round) into (row, value) exactly as frag_F does, writes
-// its value into its row of the wave's fold buffer (zeros elsewhere), and lane b < 6 then folds
-// row b in typical-pod order.  Rows: 0 Q1, 1 Q2 (+ Q3's frag part), 2 Q4, 3 XL, 4 XR, 5 NA.
+// its value into its row of the wave's fold buffer, and lane b < 6 then folds row b in typical-pod
+// order.  Rows: 0 Q1, 1 Q2 (+ Q3's frag part), 2 Q4, 3 XL, 4 XR, 5 NA.  The buffer is all +0.0
+// between evaluations (the kernel zeroes it once; a lane stores one cell and puts +0.0 back after
+// the fold), so the other five rows of a column read as zeros without six stores per lane.
 // Every bin receives the same sequence of fp64 adds as frag_F's (+0.0 for the typical pods that
 // do not touch it, the identity on these non-negative sums), and F adds the bins in index order
 // 0,1,3,4,5,6, so F is bit-identical.  All lanes return F.
@@ -308,8 +310,9 @@ __device__ __forceinline__ double wave_F(int cpuL, const uint32_t (&g)[4], int t
     row = t < nt ? row : -1;
     const double y = fr * (double)(int)frag;  // Q3: frag part to Q2
     const double val = (!is_cpu && acc_ok && cpu_ok && gpu_ok) ? y : x;
-#pragma unroll
-    for (int b = 0; b < kFoldRows; ++b) buf[b * kFoldStride + lane] = row == b ? val : 0.0;
+    // the buffer is all +0.0 between evaluations: a lane stores its one cell (none past the last typical pod)
+    double* cell = buf + row * kFoldStride + lane;
+    if (row >= 0) *cell = val;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     // lane b < 6 folds row b in typical-pod order; columns past the chunk's last typical pod hold
@@ -339,6 +342,9 @@ __device__ __forceinline__ double wave_F(int cpuL, const uint32_t (&g)[4], int t
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
+    // back to +0.0, not waited for: a wave's LDS operations execute in order, so this lands after the
+    // fold's reads above and before the wave's next store to the cell
+    if (row >= 0) *cell = 0.0;
   }
   // FragAmountSumExceptQ3 (frag.go:411-418): Q1 + Q2 + Q4 + XL + XR + NA, in this order
   double out = 0.0;
@@ -830,6 +836,8 @@ __global__ __launch_bounds__(kMBlock) void k_memo(MemoArgs a, const TypDev* __re
     s_keys[x] = k;
   }
   __syncthreads();
+  // wave_F's invariant: every fold buffer is all +0.0 between evaluations (s_F0 above aliased them)
+  for (int i = tid; i < a.nfw * kFoldBuf; i += kMBlock) s_fold[i] = 0.0;
   for (int j = wv; j < Cw; j += kMWaves) {  // feasible nodes per class
     int c = 0;
     for (int i0 = 0; i0 < N; i0 += 64) c += __popcll(__ballot(i0 + lane < N && s_keys[(size_t)j * N + i0 + lane] != 0u));
