@@ -2629,8 +2629,8 @@ static int launch_memo(ksim_engine* e, const RunEnv& env, const MemoPlan& pl, in
     std::vector<int> evo((size_t)TS);
     KSIM_HIP(hipMemcpy(evo.data(), e->d_m_evo.p, sizeof(int) * TS, hipMemcpyDeviceToHost));
     auto at = [&](int w, int s, int k) { return (double)h[((size_t)w * TS + s) * kT + k]; };
-    double crit = 0, hand = 0, hmax = 0, period = 0, lag = 0, f0 = 0, spin = 0;
-    int nc = 0, nh = 0, nf = 0;
+    double crit = 0, hand = 0, hmax = 0, period = 0, lag = 0, f0 = 0, spin = 0, nhand = 0;
+    int nc = 0, nh = 0, nf = 0, nn = 0;
     for (int s = 1; s + 1 < TS; ++s) {
       if (evo[s] < 0 || evo[s + 1] < 0) continue;
       const int o = evo[s] >> 16, o2 = evo[s + 1] >> 16;
@@ -2642,6 +2642,10 @@ static int launch_memo(ksim_engine* e, const RunEnv& env, const MemoPlan& pl, in
       }
       period += at(o2, s + 1, 1) - at(o, s, 1);
       if (o2 != o) lag += at(o2, s + 1, 0) - at(o2, s, 1);  // next owner: receive s -> start s+1
+      if (o2 != o) {  // the hand-off the chain goes through: the next owner's own receive, not the mean of all
+        nhand += at(o2, s, 1) - at(o, s, 1);
+        ++nn;
+      }
       ++nc;
       for (int w = 0; w < K; ++w) {
         if (w == o) continue;
@@ -2653,9 +2657,10 @@ static int launch_memo(ksim_engine* e, const RunEnv& env, const MemoPlan& pl, in
     }
     if (nc && nh)
       std::fprintf(stderr, "ksim memo trace (replica 0, %d steps, us): owner start->publish %.3f; publish->receive mean %.3f max %.3f; "
-                   "next owner receive->start %.3f; publish->publish %.3f; owner start->all F done %.3f, ->fresh key %.3f\n",
+                   "next owner receive->start %.3f; publish->publish %.3f; owner start->all F done %.3f, ->fresh key %.3f; "
+                   "next owner publish->receive %.3f (%d of %d steps hand over)\n",
                    TS, crit / nc / 100, hand / nh / 100, hmax / 100, lag / nc / 100, period / nc / 100,
-                   nf ? f0 / nf / 100 : 0.0, nf ? (f0 + spin) / nf / 100 : 0.0);
+                   nf ? f0 / nf / 100 : 0.0, nf ? (f0 + spin) / nf / 100 : 0.0, nn ? nhand / nn / 100 : 0.0, nn, nc);
   }
   if (profile) {
     KSIM_HIP(hipStreamSynchronize(st));

@@ -23,7 +23,9 @@
 //      Reserve's GPU selector and publishes {node, mask} as one 4-byte granule win[s] (written
 //      once per run, so no slot reuse and no tag), and writes the result;
 //   3. the owner of the NEXT create event's class computes that class's top-2 keys (all fresh
-//      but the node step s will change -- the exclusion in 2 handles it);
+//      but the node step s will change -- the exclusion in 2 handles it): its idle waves scan
+//      every node but d during 1, and d's fresh key is merged in once it is stored, so nothing
+//      of the scan stands between the refresh and the poll in 4;
 //   4. every workgroup reads win[s] (relaxed agent-scope poll) and applies the Bind to its LDS
 //      copy of the cluster; that node is the next step's d.
 // Delete events need no exchange: every workgroup reads the creation's granule and unbinds.
@@ -40,6 +42,12 @@ constexpr int kMaxCw = 64;                 // class slots per workgroup (one wav
 constexpr int kMaxItems = 1 + 8 * kMaxCw;  // F evaluations per refresh: current + 8 per request
 constexpr int kFoldRows = 6;               // Q1, Q2 (+Q3 frag), Q4, XL, XR, NA
 constexpr int kCritWaves = 9;              // owner: waves 1..9 evaluate the step's class on d
+// waves that scan the next create event's class for its top-2 during phase A (bit w = wave w): outside wave 0,
+// the owner's critical waves and the list wave, the same on every workgroup
+constexpr unsigned kScanMask = 0x7C00u;    // waves 10-14
+constexpr int kScanWaves = __builtin_popcount(kScanMask);
+static_assert((kScanMask & ((2u << kCritWaves) - 1u)) == 0u && (kScanMask >> (kMWaves - 1)) == 0u,
+              "the scan waves are idle in phase A on an owner too");
 // fold-buffer rows 66 doubles apart: lanes 0-5 fold rows 0-5 with ds_read_b128, whose bank is
 // (a/4) % 64; a 64-double (2 x 256 B) stride put all six rows on the same banks (6-way conflict),
 // 66 puts row b on banks 4b..4b+3
@@ -742,10 +750,11 @@ __device__ void memo_decider(const MemoArgs& a, const ReplicaDev& rp, MemoShared
 //   A  owner of the step's class: waves 0-8 evaluate F of d's current state and of its candidate
 //      states for that class (no list: wave k <-> candidate k) -- the critical path;
 //      list wave (15): the work list of d's other requests;
+//      next step's owner, waves 10-14 (kScanMask): per-wave top-2 of its class without d;
 //   B  owner: wave 0 scores, updates the class group's keys, takes the winner and publishes;
 //      the other waves evaluate the listed states;
-//   C  list wave: the listed requests' keys; then (next step's owner) top-2; then wave 0 reads
-//      the step's granule and applies the Bind.
+//   C  list wave: the listed requests' keys, then (next step's owner) the scan's pairs and d's
+//      fresh key merged into the top-2; wave 0 reads the step's granule and applies the Bind.
 // ---------------------------------------------------------------------------
 // kDecider: decider mode (MemoArgs::decider), a separate instantiation so that the classic
 // kernel's register allocation does not carry the decider's code.
@@ -994,6 +1003,21 @@ __global__ __launch_bounds__(kMBlock) void k_memo(MemoArgs a, const TypDev* __re
     const bool own = !kDecider && oc >= 0 && (oc >> 16) == w;  // decider mode: workgroup 0 decides
     const int oslot = own ? (oc & 0xff) : -1;
     const int crep = own ? ((oc >> 8) & 0xff) : -1;
+    // the slot of the next event's class when it is a create this workgroup owns (lean: and the class is not
+    // dead already -- the skip path takes its top-2 after the run of dead events), else -1
+    int nslot = -1;
+    if constexpr (!kDecider) {
+      if (step + 1 < rp.n_events) {
+        const int ocn = __builtin_amdgcn_readfirstlane(sh.evo[eb + 1]);
+        if (ocn >= 0 && (ocn >> 16) == w) {
+          nslot = ocn & 0xff;
+          if constexpr (kSkip) {
+            const int cn = __builtin_amdgcn_readfirstlane(sh.cls_id[nslot]);
+            if (skip_ok && ((sh.dead[cn >> 5] >> (cn & 31)) & 1u)) nslot = -1;
+          }
+        }
+      }
+    }
     const unsigned long long t_loaded = prof ? __builtin_amdgcn_s_memrealtime() : 0ull;
     if (prof && tid == 0) sh.prof[14] += t_loaded - t_last;  // step start: the event / d loads
 
@@ -1059,6 +1083,21 @@ __global__ __launch_bounds__(kMBlock) void k_memo(MemoArgs a, const TypDev* __re
           sh.nitems = tot > 0 ? i0 + tot : 0;
           if (prof) sh.prof[12] += __builtin_amdgcn_s_memrealtime() - tl0;
         }
+      }
+    }
+    // ---- A, the waves with nothing else to do: per-wave top-2 of the next create event's class over every node
+    // but d.  A step writes keys of column d only (wave 0's own group here, the list wave in C), so the scan races
+    // with nothing; the list wave merges d's fresh key in after C.
+    if constexpr (!kDecider) {
+      if (nslot >= 0 && ((kScanMask >> wv) & 1u)) {
+        const unsigned* kr = s_keys + (size_t)nslot * N;
+        unsigned a1 = 0u, a2 = 0u;
+        for (int i = __popc(kScanMask & ((1u << wv) - 1u)) * 64 + lane; i < N; i += kScanWaves * 64) {
+          const unsigned k = i != d ? kr[i] : 0u;
+          if (k > a1) { a2 = a1; a1 = k; } else if (k > a2) { a2 = k; }
+        }
+        wave_top2(a1, a2);
+        if (lane == 0) { sh.wtop[wv][0] = a1; sh.wtop[wv][1] = a2; }
       }
     }
     // ---- the owner publishes the step's winner (wave 0, as soon as waves 1-9 have their F).
@@ -1187,6 +1226,7 @@ __global__ __launch_bounds__(kMBlock) void k_memo(MemoArgs a, const TypDev* __re
     __syncthreads();
     mark(5);
     // ---- C: the listed requests' keys (list wave)
+    unsigned nk_l = 0u;  // list wave, lane j: the key it stored for (slot j, d)
     if (d >= 0 && wv == kLW) {
       const unsigned long long tl0 = prof ? __builtin_amdgcn_s_memrealtime() : 0ull;
       const int nit = __builtin_amdgcn_readfirstlane(sh.nitems);
@@ -1208,13 +1248,18 @@ __global__ __launch_bounds__(kMBlock) void k_memo(MemoArgs a, const TypDev* __re
         unsigned* kp = s_keys + (size_t)lane * N + d;
         const unsigned old = *kp;
         *kp = nk;
+        nk_l = nk;
         sh.cnt[lane] += (nk != 0u ? 1 : 0) - (old != 0u ? 1 : 0);
       }
       if (prof && lane == 0) sh.prof[13] += __builtin_amdgcn_s_memrealtime() - tl0;
     }
     mark(6);
-    // ---- top-2 of the next create event's class (its owner), on keys fresh but for this step's node;
-    // decider mode: the top list of event step + kLag on keys fresh up to event step - 1
+    // ---- top-2 of the next create event's class (its owner), on keys fresh but for this step's node: the list
+    // wave reduces the scan waves' pairs (over every node but d, left in sh.wtop before the barrier after A) and
+    // merges d's fresh key in -- top2(S) = merge2(top2(S \ {d}), key_d).  That key is the one this wave has just
+    // stored, or the one wave 0 stored for the step's own group before the barrier after A.  The consumer is
+    // wave 0 at the next step's start, behind the end-of-step barrier: no barrier here.
+    // Decider mode: the top list of event step + kLag on keys fresh up to event step - 1.
     if constexpr (kDecider) {
       if (step + kLag < rp.n_events) {
         const int ocn = __builtin_amdgcn_readfirstlane(sh.evo[eb + kLag]);
@@ -1223,12 +1268,19 @@ __global__ __launch_bounds__(kMBlock) void k_memo(MemoArgs a, const TypDev* __re
           publish_top(ocn & 0xff, step + kLag);
         }
       }
-    } else if (step + 1 < rp.n_events) {
-      const int ocn = __builtin_amdgcn_readfirstlane(sh.evo[eb + 1]);
-      if (ocn >= 0 && (ocn >> 16) == w) {
-        __syncthreads();
-        top2(ocn & 0xff);
+    } else if (nslot >= 0 && wv == kLW) {
+      // pair k of the scan waves on lane k
+      int sw = -1;
+#pragma unroll
+      for (int k = 0, m = (int)kScanMask; k < kScanWaves; ++k, m &= m - 1) sw = lane == k ? __builtin_ctz(m) : sw;
+      unsigned a1 = sw >= 0 ? sh.wtop[sw][0] : 0u, a2 = sw >= 0 ? sh.wtop[sw][1] : 0u;
+      wave_top2(a1, a2);
+      if (d >= 0) {
+        const bool own_grp = ((__ballot(r_skip) >> nslot) & 1ull) != 0ull;
+        const unsigned fk = own_grp ? s_keys[(size_t)nslot * N + d] : (unsigned)__builtin_amdgcn_readlane((int)nk_l, nslot);
+        merge2(a1, a2, fk, 0u);
       }
+      if (lane == 0) { sh.t2a = a1; sh.t2b = a2; }
     }
     mark(7);
     if constexpr (kDelays) hdelay(a.delay, 1, step, wv, (int)blockIdx.x);
