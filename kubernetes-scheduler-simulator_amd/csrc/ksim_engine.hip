@@ -47,8 +47,10 @@
 
 #include "ksim_device.hpp"
 #include "ksim_engine.h"
+#include "ksim_plan.hpp"
 
 using namespace ksim;
+using namespace ksim_plan;
 
 namespace {
 
@@ -1779,8 +1781,43 @@ __global__ __launch_bounds__(64) void k_reserve(ReplicaDev* reps, const TypDev* 
 // ---------------------------------------------------------------------------
 // Host engine object
 // ---------------------------------------------------------------------------
-struct MemoPlan;
-struct HPlan;
+// The memoised FGD replays: each kernel's plan (ksim_plan.hpp), whether it holds, the replicas it was made for, and
+// the device tables uploaded from it.
+struct MemoState {  // k_memo
+  MemoPlan plan;  // uploaded before the timed run
+  bool ok = false;
+  std::vector<int> reps;
+  DevBuf<PodDev> pod;
+  DevBuf<int> owner, wgcls, wgref;
+  DevBuf<unsigned long long> wggrp;
+  DevBuf<int> evo;
+  DevBuf<int> evcls;       // decider mode: class of each event
+  DevBuf<unsigned> hkeys;  // the keys in HBM (MemoPlan::hkeys)
+  DevBuf<int> wgmap;       // each block's launch position << 8 | workgroup (MemoArgs::wg_map)
+  DevBuf<unsigned> win;
+  DevBuf<unsigned> topg;   // decider mode: top granules
+};
+struct HMemoState {  // k_hmemo (the keys in HBM)
+  HPlan plan;
+  bool ok = false;
+  std::vector<int> reps;
+  DevBuf<int> cg;
+  DevBuf<PodDev> cls;
+  DevBuf<uint16_t> cgrp;
+  DevBuf<PodDev> gpod;
+  DevBuf<int> mtoff;  // the per-model tables (typed replicas)
+  DevBuf<uint8_t> mtab;
+  DevBuf<double> na;  // their NA bins per (model, total), k_hinit_na
+  DevBuf<int> evc;
+  DevBuf<NodeRec> st;
+  DevBuf<int> ns, nstate;
+  DevBuf<unsigned> gsc, keys, l1;
+  DevBuf<unsigned> l2;  // initial second maxima (HPlan::l2)
+  DevBuf<int> cnt;
+  DevBuf<unsigned long long> prof;
+  DevBuf<uint8_t> hist;  // the wide form with deletes: per-workgroup bind history
+};
+
 // Every device resource is a member handle (ksim_host.hpp) that frees itself: a new buffer is one new member and nothing
 // else.  Declaration order carries meaning, since members go in reverse: the streams come first and so go last, after
 // every buffer and event used on them.  Before that the destructor sets the device, drains the side streams and then
@@ -1830,53 +1867,20 @@ struct ksim_engine {
   std::vector<std::vector<TypDev>> h_tp;  // each replica's typical table as uploaded (k_hmemo's per-model tables)
   std::vector<std::vector<int>> h_cls_n;
   std::vector<std::vector<int>> h_ev_cls;  // class of each event, -1 delete
-  DevBuf<PodDev> d_m_pod;
-  DevBuf<int> d_m_owner;
-  DevBuf<int> d_m_wgcls;
-  DevBuf<int> d_m_wgref;
-  DevBuf<unsigned long long> d_m_wggrp;
-  DevBuf<unsigned> d_win;
-  DevBuf<int> d_m_evo;
-  DevBuf<int> d_m_evcls;     // decider mode: class of each event
-  DevBuf<unsigned> d_topg;   // decider mode: top granules
-  DevBuf<unsigned> d_m_hkeys;  // k_memo with the keys in HBM (MemoPlan::hkeys)
-  DevBuf<int> d_m_wgmap;       // k_memo: each block's launch position << 8 | workgroup (MemoArgs::wg_map)
+  MemoState memo;
+  HMemoState hmemo;
+  // their cache key: the plans hold until events, policies, nodes, typical tables or hints change
+  bool mplan_dirty = true;
+  std::vector<int> mplan_all;  // the FGD replicas the plans were made for
+  int mplan_max_ev = -1;
+  bool split_fgd = false;      // the wide-hinted FGD replicas on k_memo beside the others on k_hmemo (one run)
   DevBuf<unsigned long long> d_done;  // [2 + R] the overlapped report's queue (ksim_scan1.hpp Scan1Args::done)
   DevBuf<__int128> d_ragg;     // [R][kScanPartsMax][2][kFields] the multi-workgroup report scan's part sums
   unsigned done_epoch = 0;
   DevEvent ev_ovl;    // the queue's tickets zeroed (the report's stream waits on it)
   DevBuf<double> d_th;       // FGD score steps (build_score_thresholds), null if unusable
-  std::unique_ptr<MemoPlan> mplan;  // the FGD replicas' k_memo plan, uploaded before the timed run
-  bool mplan_dirty = true;           // events or policies changed since the plan was made
-  bool mplan_ok = false;
-  std::vector<int> mplan_all;   // the FGD replicas the plans were made for (cache key)
-  std::vector<int> mplan_reps;  // the replicas of the k_memo plan
-  std::vector<int> hplan_reps;  // the replicas of the k_hmemo plan
   std::vector<int> wgs_hint;    // per replica: workgroups asked by ksim_engine_set_replica_wgs (0: the engine's choice)
-  bool split_fgd = false;       // the wide-hinted FGD replicas on k_memo beside the others on k_hmemo (one run)
-  int mplan_max_ev = -1;
   int last_memo = 0;
-  // k_hmemo (memoised FGD replay, keys in HBM): the plan and its device tables
-  std::unique_ptr<HPlan> hplan;
-  bool hplan_ok = false;
-  DevBuf<int> d_h_cg;
-  DevBuf<PodDev> d_h_cls;
-  DevBuf<uint16_t> d_h_cgrp;
-  DevBuf<PodDev> d_h_gpod;
-  DevBuf<int> d_h_mtoff;      // k_hmemo's per-model tables (typed replicas)
-  DevBuf<uint8_t> d_h_mtab;
-  DevBuf<double> d_h_na;      // their NA bins per (model, total), k_hinit_na
-  DevBuf<int> d_h_evc;
-  DevBuf<NodeRec> d_h_st;
-  DevBuf<int> d_h_ns;
-  DevBuf<int> d_h_nstate;
-  DevBuf<unsigned> d_h_gsc;
-  DevBuf<unsigned> d_h_keys;
-  DevBuf<unsigned> d_h_l1;
-  DevBuf<unsigned> d_h_l2;  // k_hmemo: initial second maxima (HPlan::l2)
-  DevBuf<int> d_h_cnt;
-  DevBuf<unsigned long long> d_h_prof;
-  DevBuf<uint8_t> d_h_hist;  // wide k_hmemo with deletes: per-workgroup bind history
   int last_hmemo = 0;
   int last_rgo = 0;  // replicas the last run replayed on k_random_go
   int last_scan1 = 0;  // replicas the last run replayed on k_scan1
@@ -2047,174 +2051,41 @@ static const void* replay_kernel(int pol, int K, bool general) {
   }
 }
 
-// ---- k_memo planning (memoised FGD replay, ksim_memo.hpp) ----
-struct MemoPlan {
-  int K = 0, Cw = 0, nfw = 0, Cmax = 1;  // K: the most workgroups of a replica
-  int nwg = 0;                            // workgroups of the launch (Σ Kr)
-  std::vector<int> Kr, wgoff;             // [Rg] each replica's workgroups (r06: per replica), its first block
-  bool decider = false;  // workgroup 0 decides, 1..K-1 own the classes
-  bool hkeys = false;    // the keys in HBM (k_memo<..., kHKeys>): classes whose keys do not fit in LDS
-  size_t lds = 0;
-  std::vector<PodDev> pod;                  // [Rg][Cmax]
-  std::vector<int> owner;                   // [Rg][Cmax]
-  std::vector<int> wgcls, wgref;            // [nwg][Cw] (block wgoff[i] + w)
-  std::vector<unsigned long long> wggrp;    // [nwg][Cw]
-};
-
-// Classes of one replica onto K workgroups, at most Cw slots each.  Classes with the same score
-// request (cpu_nz, milli, num) stay in one workgroup (their candidate states are the same, so one
-// refresh evaluates them once); groups go largest first to the workgroup with the fewest groups.
-// split: a group that fits no workgroup whole is spread over the workgroups with the most free slots
-// (each part's workgroup evaluates the group's candidate states for its own classes: the same keys,
-// the states evaluated once per part) -- the typed gpuspec traces hold groups of up to 60 classes.
-static bool memo_assign(const std::vector<PodDev>& cls, int K, int Cw, std::vector<int>& slot_cls, std::vector<int>& owner,
-                        bool split = false) {
-  std::vector<std::pair<std::vector<int32_t>, std::vector<int>>> groups;
-  for (int c = 0; c < (int)cls.size(); ++c) {
-    const std::vector<int32_t> k{cls[c].cpu_nz, cls[c].milli, cls[c].num};
-    auto it = std::find_if(groups.begin(), groups.end(), [&](const auto& g) { return g.first == k; });
-    if (it == groups.end()) groups.push_back({k, {c}});
-    else it->second.push_back(c);
+// ---- k_memo / k_hmemo: the plans (ksim_plan.hpp) onto the device ----
+// The instantiation of each form (memo_form, hmemo_form): the only place that names them.  No default: a form with no
+// instantiation is a compiler warning here, and a null kernel the launch refuses.
+static const void* memo_kernel(MemoForm f) {
+  using ksim_memo::k_memo;
+  switch ((MemoFormCode)f.code()) {
+    case kMemoLean: return (const void*)k_memo<false, false>;
+    case kMemoDecider: return (const void*)k_memo<true, true>;
+    case kMemoGeneral: return (const void*)k_memo<false, true>;
+    case kMemoStress: return (const void*)k_memo<false, false, true>;
+    case kMemoReport: return (const void*)k_memo<false, false, false, true>;
+    case kMemoHKeysLean: return (const void*)k_memo<false, false, false, false, true>;
+    case kMemoHKeysGeneral: return (const void*)k_memo<false, true, false, false, true>;
+    case kMemoHKeysReport: return (const void*)k_memo<false, false, false, true, true>;
   }
-  std::stable_sort(groups.begin(), groups.end(),
-                   [](const auto& a, const auto& b) { return a.second.size() > b.second.size(); });
-  std::vector<int> used(K, 0), ng(K, 0);
-  slot_cls.assign((size_t)K * Cw, -1);
-  owner.assign(cls.size(), -1);
-  for (const auto& g : groups) {
-    const int sz = (int)g.second.size();
-    int best = -1;
-    for (int w = 0; w < K; ++w)
-      if (used[w] + sz <= Cw && (best < 0 || ng[w] < ng[best] || (ng[w] == ng[best] && used[w] < used[best]))) best = w;
-    if (best < 0 && !split) return false;
-    for (size_t k = 0; k < g.second.size();) {
-      if (best < 0 || used[best] >= Cw) {  // split: the workgroup with the most free slots
-        best = 0;
-        for (int w = 1; w < K; ++w)
-          if (used[w] < used[best]) best = w;
-        if (used[best] >= Cw) return false;
-        ++ng[best];
-      } else if (k == 0) {
-        ++ng[best];
-      }
-      const int c = g.second[k++];
-      slot_cls[(size_t)best * Cw + used[best]] = c;
-      owner[c] = (best << 8) | used[best];
-      ++used[best];
-    }
-  }
-  return true;
+  return nullptr;
 }
-
-// forceK > 0: exactly that many workgroups per replica (a wide-hinted group, ksim_engine_set_replica_wgs);
-// forceKr: that many for each replica (r06: the hints differ); hkeys_ok: when no K fits the keys in LDS, the keys
-// may go to HBM (k_memo<..., kHKeys>, classes split over the workgroups as evenly as the slots allow).
-static bool memo_plan(const ksim_engine* e, const std::vector<int>& reps, MemoPlan& pl, int forceK = 0,
-                      bool hkeys_ok = false, const std::vector<int>* forceKr = nullptr) {
-  using namespace ksim_memo;
-  const int Rg = (int)reps.size();
-  if (Rg == 0 || e->N > kMemoMaxRank + 1) return false;
-  pl.Cmax = 1;
-  for (int r : reps) pl.Cmax = std::max(pl.Cmax, (int)e->h_cls[r].size());
-  const int K0 = forceK > 0 ? forceK : e->wgs_req > 0 ? e->wgs_req : std::min(64, e->cus / Rg);
-  std::vector<int> Kr(Rg, K0);
-  if (forceKr) Kr = *forceKr;
-  if ((int)Kr.size() != Rg) return false;
-  auto total = [&]() { int t = 0; for (int k : Kr) t += k; return t; };
-  auto kmax = [&]() { return *std::max_element(Kr.begin(), Kr.end()); };
-  if (*std::min_element(Kr.begin(), Kr.end()) < 1 || kmax() > 64 || total() > e->cus) return false;
-  const bool forced = forceK > 0 || forceKr != nullptr;
-  const int d0 = pl.decider ? 1 : 0;  // decider mode: classes on workgroups 1..K-1
-  std::vector<std::vector<int>> sc(Rg), ow(Rg);
-  // the smallest Cw >= Cw0 every replica's classes pack into (split: parts of a group on several workgroups)
-  auto pack = [&](int Cw0, bool split) {
-    for (int Cw = Cw0; Cw <= kMaxCw; ++Cw) {
-      bool ok = true;
-      for (int i = 0; ok && i < Rg; ++i) {
-        const int K = Kr[i];
-        std::vector<int> s1;
-        ok = K > d0 && memo_assign(e->h_cls[reps[i]], K - d0, Cw, s1, ow[i], split);
-        if (!ok) break;
-        sc[i].assign((size_t)K * Cw, -1);
-        std::copy(s1.begin(), s1.end(), sc[i].begin() + (size_t)d0 * Cw);
-        for (int& o : ow[i]) o += d0 << 8;
-      }
-      if (ok) return Cw;
-    }
-    return 0;
-  };
-  auto cw0 = [&](int dd) {  // the fewest slots per workgroup that can hold every replica's classes
-    int c = 1;
-    for (int i = 0; i < Rg; ++i) c = std::max(c, ((int)e->h_cls[reps[i]].size() + Kr[i] - 1 - dd) / std::max(1, Kr[i] - dd));
-    return c;
-  };
-  auto fold_waves = [&](int Cw, bool hk) {  // waves 1..9 need fold buffers on the critical path
-    for (int f : {16, 12})
-      if (memo_lds(e->N, Cw, f, hk) <= 160 * 1024) return f;
-    return 0;
-  };
-  const void* fcap = (const void*)ksim_memo::k_memo<false, false>;
-  int Cw = 0, nfw = 0;
-  bool hk = false;
-  for (;;) {
-    Cw = pack(cw0(d0), false);
-    nfw = Cw > 0 ? fold_waves(Cw, false) : 0;
-    // every workgroup of the launch must be resident (they exchange granules every step)
-    if (nfw > 0 && kmax() > 1 && total() > resident_cap(e, fcap, memo_lds(e->N, Cw, nfw)))
-      return false;
-    if (nfw > 0) break;
-    if (hkeys_ok && !pl.decider) {  // the keys in HBM: LDS holds the cluster and the fold buffers only
-      Cw = pack(cw0(0), true);
-      nfw = Cw > 0 ? fold_waves(Cw, true) : 0;
-      if (nfw > 0 && kmax() > 1 && total() > resident_cap(e, fcap, memo_lds(e->N, Cw, nfw, true))) return false;
-      if (nfw > 0) {
-        hk = true;
-        break;
-      }
-    }
-    const int K = Kr[0];
-    if (forced || e->wgs_req > 0 || K >= 64 || Rg * (K + 1) > e->cus) return false;
-    std::fill(Kr.begin(), Kr.end(), K + 1);
+static const void* hmemo_kernel(HMemoForm f) {
+  using ksim_hmemo::k_hmemo;
+  using ksim_hmemo::k_hmemo_group;
+  switch ((HMemoFormCode)f.code()) {
+    case kHMemoOne: return (const void*)k_hmemo<0, false>;
+    case kHMemoOneProf: return (const void*)k_hmemo<0, true>;
+    case kHMemoOneModel: return (const void*)k_hmemo<0, false, true>;
+    case kHMemoOneProfModel: return (const void*)k_hmemo<0, true, true>;
+    case kHMemoWide: return (const void*)k_hmemo<1, false>;
+    case kHMemoWideProf: return (const void*)k_hmemo<1, true>;
+    case kHMemoWide4: return (const void*)k_hmemo<4, false>;
+    case kHMemoWide4Prof: return (const void*)k_hmemo<4, true>;
+    case kHMemoGroup: return (const void*)k_hmemo_group<1, false>;
+    case kHMemoGroupProf: return (const void*)k_hmemo_group<1, true>;
+    case kHMemoGroup4: return (const void*)k_hmemo_group<4, false>;
+    case kHMemoGroup4Prof: return (const void*)k_hmemo_group<4, true>;
   }
-  pl.K = kmax();
-  pl.nwg = total();
-  pl.Kr = Kr;
-  pl.wgoff.assign(Rg, 0);
-  for (int i = 1; i < Rg; ++i) pl.wgoff[i] = pl.wgoff[i - 1] + Kr[i - 1];
-  pl.Cw = Cw;
-  pl.nfw = nfw;
-  pl.hkeys = hk;
-  pl.lds = memo_lds(e->N, Cw, nfw, hk);
-  pl.pod.assign((size_t)Rg * pl.Cmax, PodDev{});
-  pl.owner.assign((size_t)Rg * pl.Cmax, -1);
-  pl.wgcls.assign((size_t)pl.nwg * Cw, -1);
-  pl.wgref.assign((size_t)pl.nwg * Cw, 0);
-  pl.wggrp.assign((size_t)pl.nwg * Cw, 0ull);
-  for (int i = 0; i < Rg; ++i) {
-    const std::vector<PodDev>& cls = e->h_cls[reps[i]];
-    for (size_t c = 0; c < cls.size(); ++c) {
-      pl.pod[(size_t)i * pl.Cmax + c] = cls[c];
-      pl.owner[(size_t)i * pl.Cmax + c] = ow[i][c];
-    }
-    for (int w = 0; w < Kr[i]; ++w) {
-      const size_t o = ((size_t)pl.wgoff[i] + w) * Cw;
-      for (int j = 0; j < Cw; ++j) {
-        const int c = sc[i][(size_t)w * Cw + j];
-        pl.wgcls[o + j] = c;
-        pl.wgref[o + j] = j;
-        if (c < 0) continue;
-        for (int j2 = 0; j2 < j; ++j2) {  // first slot with the same score request
-          const int c2 = sc[i][(size_t)w * Cw + j2];
-          if (c2 >= 0 && cls[c2].cpu_nz == cls[c].cpu_nz && cls[c2].milli == cls[c].milli && cls[c2].num == cls[c].num) {
-            pl.wgref[o + j] = j2;
-            break;
-          }
-        }
-        pl.wggrp[o + pl.wgref[o + j]] |= 1ull << j;
-      }
-    }
-  }
-  return true;
+  return nullptr;
 }
 
 // The FGD score steps, built once per process on the host (nullptr if the check fails: k_memo
@@ -2233,221 +2104,64 @@ static int ensure_score_table(ksim_engine* e, hipStream_t st) {
   return KSIM_OK;
 }
 
-// ---- k_hmemo planning (memoised FGD replay with the keys in HBM, ksim_hmemo.hpp) ----
-struct HPlan {
-  int Cmax = 1, Gmax = 1, Smax = 1, Npad = 0, nb = 0;
-  int K = 1, S = 0, nbw = 0;      // workgroups per replica, ranks per workgroup, L1 blocks per workgroup
-  bool l2 = false;                // the second maxima beside L1 (the wide form, when they fit in LDS; KSIM_VARIANT hl2)
-  size_t lds = 0;
-  std::vector<int> cg;            // [Rg][2] classes, groups
-  std::vector<PodDev> cls, gpod;  // [Rg][Cmax] (sorted by group), [Rg][Gmax]
-  std::vector<uint16_t> cgrp;     // [Rg][Cmax]
-  std::vector<int> evc;           // [Rg][stride] class slot of each event, -1 delete
-  std::vector<NodeRec> st;        // [Rg][Smax] distinct initial node states
-  std::vector<int> ns;            // [Rg]
-  std::vector<int> nstate;        // [Rg][Npad] state of each rank, -1 padding
-  // Typed replicas (a GPU typical pod names models): per GPU model of the cluster, the typical table cut to
-  // the CPU-only pods and the GPU pods that accept the model (ksim_hmemo.hpp, "per-model tables")
-  int Mtab = 0, Mslots = 0;       // longest replica's concatenated tables, most models of one replica
-  std::vector<int> mtoff;         // [Rg][KSIM_MAX_TYPES] kMtPresent | slot << 21 | entries << 12 | offset
-  std::vector<uint8_t> mtab;      // [Rg][Mtab] typical-table index of each entry
-};
-
-// Classes of each replica grouped by score request (cpu_nz, milli, num: the candidate states of
-// fgd_score.go:99-149 depend on nothing else), and the distinct initial node states (the keys
-// before the first event depend on the state, the class and the rank only).
-static bool hmemo_plan(const ksim_engine* e, const std::vector<int>& reps, int stride, HPlan& pl, int forceK = 0,
-                       int forceS = 0) {
-  using namespace ksim_hmemo;
-  const int Rg = (int)reps.size();
-  if (Rg == 0 || e->N > kHRankMax || !score_table()) return false;
-  pl.Npad = (e->N + kFan - 1) / kFan * kFan;
-  pl.nb = pl.Npad / kFan;
-  // one workgroup per replica while one L1 level covers the cluster; wider clusters are sliced over
-  // K co-resident workgroups (at most 64: one granule column per polling lane), S a multiple of 64
-  // (run_mode 5 with wgs_per_replica > 1 asks for the wide form on a small cluster too; when the
-  // wide grid would not fit the usable CUs a small cluster keeps one workgroup per replica)
-  const bool small = e->N <= kMaxNb * kFan;
-  pl.K = 1;
-  pl.S = e->N;
-  pl.nbw = pl.nb;
-  if (forceK > 0) {  // a node-sharded group: every shard's slices alike (the caller checked S, K)
-    pl.S = forceS;
-    pl.K = forceK;
-    pl.nbw = forceS / kFan;
-  } else if (!small || (e->run_mode == 5 && e->wgs_req > 1)) {
-    const int want = e->wgs_req > 1 ? e->wgs_req : 64;
-    const int S = std::max(kFan, (e->N + want - 1) / want + kFan - 1) / kFan * kFan;
-    const int K = (e->N + S - 1) / S;
-    if (S <= kMaxNb * kFan && (size_t)Rg * K <= (size_t)e->cus) {
-      pl.S = S;
-      pl.K = K;
-      pl.nbw = S / kFan;
-    } else if (!small) {
-      return false;
-    }
-  }
-  std::vector<std::vector<int>> ord(Rg), gof(Rg), slot(Rg), gfirst(Rg), sof(Rg);
-  std::vector<std::vector<NodeRec>> sts(Rg);
-  pl.Cmax = pl.Gmax = pl.Smax = 1;
-  for (int i = 0; i < Rg; ++i) {
-    const int r = reps[i];
-    const std::vector<PodDev>& cls = e->h_cls[r];
-    std::vector<std::array<int, 3>> gk;
-    gof[i].resize(cls.size());
-    for (size_t c = 0; c < cls.size(); ++c) {
-      const std::array<int, 3> k{cls[c].cpu_nz, cls[c].milli, cls[c].num};
-      const auto it = std::find(gk.begin(), gk.end(), k);
-      gof[i][c] = (int)(it - gk.begin());
-      if (it == gk.end()) { gk.push_back(k); gfirst[i].push_back((int)c); }
-    }
-    if ((int)cls.size() > kMaxClasses || (int)gk.size() > kMaxGroups) return false;
-    ord[i].resize(cls.size());
-    std::iota(ord[i].begin(), ord[i].end(), 0);
-    std::stable_sort(ord[i].begin(), ord[i].end(), [&](int a, int b) { return gof[i][a] < gof[i][b]; });
-    slot[i].assign(cls.size(), -1);
-    for (size_t k = 0; k < ord[i].size(); ++k) slot[i][ord[i][k]] = (int)k;
-    pl.Cmax = std::max(pl.Cmax, (int)cls.size());
-    pl.Gmax = std::max(pl.Gmax, (int)gk.size());
-    // distinct initial states (every field but the rank)
-    if (e->h_rec[r].size() != (size_t)e->N) return false;
-    std::map<std::array<uint32_t, 7>, int> sid;
-    sof[i].assign(pl.Npad, -1);
-    for (int j = 0; j < e->N; ++j) {
-      const NodeRec& n = e->h_rec[r][j];
-      std::array<uint32_t, 7> k;
-      std::memcpy(k.data(), &n, sizeof k);
-      auto it = sid.find(k);
-      if (it == sid.end()) {
-        it = sid.emplace(k, (int)sts[i].size()).first;
-        sts[i].push_back(n);
-      }
-      sof[i][(int)(n.name_rank - (uint32_t)e->node_off)] = it->second;
-    }
-    pl.Smax = std::max(pl.Smax, (int)sts[i].size());
-  }
-  {
-    // L2 spares the flagged blocks' key reloads.  They bound the wide form's class waves (C5: 100k nodes, the
-    // keys far beyond L2, 55 flagged rows per refresh from HBM), while one workgroup over an openb cluster
-    // keeps its keys in L2 and is bound by F: there L2 only adds update work (profiles/r04/hmemo/).
-    // Off by default since r05: in the wide form its code alone cost C5 4.09 -> 4.22 s, and it is compiled only into
-    // the one-workgroup instantiations; KSIM_VARIANT=hl2=1 turns it on there.
-    const bool want = variant("hl2", 0) == 1 && pl.K == 1;
-    pl.l2 = want && hmemo_layout(pl.S, pl.Cmax, pl.Gmax, pl.nbw, true, 0).total <= 160 * 1024;
-  }
-  {  // per-model tables of the typed replicas (KSIM_VARIANT=hmodel=0: the whole table for every model, as before r05)
-    const bool on = variant("hmodel", 1) != 0;
-    pl.Mtab = pl.Mslots = 0;
-    pl.mtoff.assign((size_t)Rg * KSIM_MAX_TYPES, 0);
-    std::vector<std::vector<uint8_t>> mt(Rg);
-    for (int i = 0; on && pl.K == 1 && i < Rg; ++i) {  // (the wide form evaluates the whole table)
-      const int r = reps[i];
-      if (!e->reps[r].typed || e->h_tp[r].size() != (size_t)e->reps[r].nt) continue;
-      const std::vector<TypDev>& tpv = e->h_tp[r];
-      const int ncpu = e->reps[r].ncpu, nt = e->reps[r].nt;
-      uint32_t models = 0u;
-      for (const NodeRec& n : e->h_rec[r]) models |= 1u << n.gpu_type;
-      int slot = 0;
-      for (int m = 0; m < KSIM_MAX_TYPES; ++m) {
-        if (!((models >> m) & 1u)) continue;
-        const int off = (int)mt[i].size();
-        for (int t = 0; t < nt; ++t)
-          if (t < ncpu || (tpv[t].tmask >> m) & 1u) mt[i].push_back((uint8_t)t);
-        const int len = (int)mt[i].size() - off;
-        pl.mtoff[(size_t)i * KSIM_MAX_TYPES + m] = (int)(ksim_hmemo::kMtPresent | (uint32_t)slot << 21 | (uint32_t)len << 12 | (uint32_t)off);
-        ++slot;
-      }
-      pl.Mtab = std::max(pl.Mtab, (int)mt[i].size());
-      pl.Mslots = std::max(pl.Mslots, slot);
-    }
-    // tables that do not fit (a 12-bit offset, or the LDS beside the keys' L1 level): the whole-table form
-    // (KSIM_VARIANT hmodel=0), which evaluates the same bits, rather than no k_hmemo at all
-    if (pl.Mtab > 4095 || hmemo_layout(pl.S, pl.Cmax, pl.Gmax, pl.nbw, pl.l2, pl.Mtab).total > 160 * 1024) {
-      pl.Mtab = pl.Mslots = 0;
-      std::fill(pl.mtoff.begin(), pl.mtoff.end(), 0);
-      for (auto& v : mt) v.clear();
-    }
-    pl.mtab.assign((size_t)Rg * std::max(pl.Mtab, 1), 0);
-    for (int i = 0; i < Rg; ++i) std::copy(mt[i].begin(), mt[i].end(), pl.mtab.begin() + (size_t)i * std::max(pl.Mtab, 1));
-  }
-  pl.lds = hmemo_layout(pl.S, pl.Cmax, pl.Gmax, pl.nbw, pl.l2, pl.Mtab).total;
-  if (pl.lds > 160 * 1024) return false;
-  pl.cg.assign((size_t)Rg * 2, 0);
-  pl.cls.assign((size_t)Rg * pl.Cmax, PodDev{});
-  pl.cgrp.assign((size_t)Rg * pl.Cmax, 0);
-  pl.gpod.assign((size_t)Rg * pl.Gmax, PodDev{});
-  pl.evc.assign((size_t)Rg * stride, -1);
-  pl.st.assign((size_t)Rg * pl.Smax, NodeRec{});
-  pl.ns.assign(Rg, 0);
-  pl.nstate.assign((size_t)Rg * pl.Npad, -1);
-  for (int i = 0; i < Rg; ++i) {
-    const int r = reps[i];
-    const std::vector<PodDev>& cls = e->h_cls[r];
-    pl.cg[2 * i] = (int)cls.size();
-    pl.cg[2 * i + 1] = (int)gfirst[i].size();
-    for (size_t k = 0; k < ord[i].size(); ++k) {
-      pl.cls[(size_t)i * pl.Cmax + k] = cls[ord[i][k]];
-      pl.cgrp[(size_t)i * pl.Cmax + k] = (uint16_t)gof[i][ord[i][k]];
-    }
-    // a group's request: its first class's (the score part, fgd_score.go:99-149, is the group's), with the
-    // least demanding Filter part of every class of the group -- min CPU, min memory, every accepted GPU
-    // model -- so that Filter of it on a node fails only when every class of the group fails (the group
-    // pruning of k_hmemo's F list; nothing else reads these fields of a group's request)
-    for (size_t g = 0; g < gfirst[i].size(); ++g) pl.gpod[(size_t)i * pl.Gmax + g] = cls[gfirst[i][g]];
-    for (size_t c = 0; c < cls.size(); ++c) {
-      PodDev& gp = pl.gpod[(size_t)i * pl.Gmax + gof[i][c]];
-      gp.cpu_req = std::min(gp.cpu_req, cls[c].cpu_req);
-      gp.mem = std::min(gp.mem, cls[c].mem);
-      gp.tmask |= cls[c].tmask;
-    }
-    const std::vector<int>& ec = e->h_ev_cls[r];
-    for (size_t k = 0; k < ec.size(); ++k) pl.evc[(size_t)i * stride + k] = ec[k] < 0 ? -1 : slot[i][ec[k]];
-    std::copy(sts[i].begin(), sts[i].end(), pl.st.begin() + (size_t)i * pl.Smax);
-    pl.ns[i] = (int)sts[i].size();
-    std::copy(sof[i].begin(), sof[i].end(), pl.nstate.begin() + (size_t)i * pl.Npad);
-  }
-  return true;
+// What the planners read of the engine, for the replicas `reps` in launch order; residency is k_memo's.
+static PlanInput plan_input(const ksim_engine* e, const RunEnv& env, const std::vector<int>& reps, bool decider = false) {
+  PlanInput in;
+  for (int r : reps)
+    in.reps.push_back({&e->h_cls[r], &e->h_ev_cls[r], &e->h_rec[r], &e->h_tp[r], e->reps[r].typed, e->reps[r].ncpu,
+                       e->reps[r].nt});
+  in.N = e->N;
+  in.node_off = e->node_off;
+  in.cus = e->cus;
+  in.wgs_req = e->wgs_req;
+  in.run_mode = e->run_mode;
+  in.decider = decider;
+  in.hl2 = env.hl2;
+  in.hmodel = env.hmodel;
+  in.score_table = score_table() != nullptr;
+  in.resident = [e](size_t lds) { return resident_cap(e, (const void*)ksim_memo::k_memo<false, false>, lds); };
+  return in;
 }
 
-static int prepare_hmemo(ksim_engine* e, const std::vector<int>& reps, int max_ev, int forceK = 0, int forceS = 0) {
-  e->hplan_ok = false;
-  if (!e->hplan) e->hplan = std::make_unique<HPlan>();
-  HPlan& pl = *e->hplan;
+static int prepare_hmemo(ksim_engine* e, const RunEnv& env, const std::vector<int>& reps, int max_ev, int forceK = 0,
+                         int forceS = 0) {
+  e->hmemo.ok = false;
+  HPlan& pl = e->hmemo.plan;
   const int stride = std::max(max_ev, 1);
-  if (!hmemo_plan(e, reps, stride, pl, forceK, forceS)) return KSIM_OK;
+  if (!hmemo_plan(plan_input(e, env, reps), stride, pl, forceK, forceS)) return KSIM_OK;
   const int Rg = (int)reps.size();
-  e->hplan_reps = reps;
+  e->hmemo.reps = reps;
   hipStream_t st = e->stream;
   int rc;
-  if ((rc = e->d_h_cg.upload(pl.cg, st))) return rc;
-  if ((rc = e->d_h_cls.upload(pl.cls, st))) return rc;
-  if ((rc = e->d_h_cgrp.upload(pl.cgrp, st))) return rc;
-  if ((rc = e->d_h_gpod.upload(pl.gpod, st))) return rc;
-  if ((rc = e->d_h_evc.upload(pl.evc, st))) return rc;
-  if ((rc = e->d_h_st.upload(pl.st, st))) return rc;
-  if ((rc = e->d_h_ns.upload(pl.ns, st))) return rc;
-  if ((rc = e->d_h_nstate.upload(pl.nstate, st))) return rc;
-  if ((rc = e->d_h_gsc.ensure((size_t)Rg * pl.Gmax * pl.Smax))) return rc;
-  if ((rc = e->d_h_keys.ensure((size_t)Rg * pl.Cmax * pl.Npad))) return rc;
-  if ((rc = e->d_h_l1.ensure((size_t)Rg * pl.Cmax * pl.nb))) return rc;
-  if (pl.l2 && (rc = e->d_h_l2.ensure((size_t)Rg * pl.Cmax * pl.nb))) return rc;
-  if ((rc = e->d_h_cnt.ensure((size_t)Rg * pl.Cmax))) return rc;
+  if ((rc = e->hmemo.cg.upload(pl.cg, st))) return rc;
+  if ((rc = e->hmemo.cls.upload(pl.cls, st))) return rc;
+  if ((rc = e->hmemo.cgrp.upload(pl.cgrp, st))) return rc;
+  if ((rc = e->hmemo.gpod.upload(pl.gpod, st))) return rc;
+  if ((rc = e->hmemo.evc.upload(pl.evc, st))) return rc;
+  if ((rc = e->hmemo.st.upload(pl.st, st))) return rc;
+  if ((rc = e->hmemo.ns.upload(pl.ns, st))) return rc;
+  if ((rc = e->hmemo.nstate.upload(pl.nstate, st))) return rc;
+  if ((rc = e->hmemo.gsc.ensure((size_t)Rg * pl.Gmax * pl.Smax))) return rc;
+  if ((rc = e->hmemo.keys.ensure((size_t)Rg * pl.Cmax * pl.Npad))) return rc;
+  if ((rc = e->hmemo.l1.ensure((size_t)Rg * pl.Cmax * pl.nb))) return rc;
+  if (pl.l2 && (rc = e->hmemo.l2.ensure((size_t)Rg * pl.Cmax * pl.nb))) return rc;
+  if ((rc = e->hmemo.cnt.ensure((size_t)Rg * pl.Cmax))) return rc;
   if (pl.Mtab > 0) {
-    if ((rc = e->d_h_mtoff.upload(pl.mtoff, st))) return rc;
-    if ((rc = e->d_h_mtab.upload(pl.mtab, st))) return rc;
-    if ((rc = e->d_h_na.ensure((size_t)Rg * pl.Mslots * ksim_hmemo::kNaStride))) return rc;
+    if ((rc = e->hmemo.mtoff.upload(pl.mtoff, st))) return rc;
+    if ((rc = e->hmemo.mtab.upload(pl.mtab, st))) return rc;
+    if ((rc = e->hmemo.na.ensure((size_t)Rg * pl.Mslots * ksim_hmemo::kNaStride))) return rc;
   }
   if ((rc = ensure_score_table(e, st))) return rc;
   KSIM_HIP(hipStreamSynchronize(st));  // the host vectors are pageable
-  e->hplan_ok = true;
+  e->hmemo.ok = true;
   return KSIM_OK;
 }
 
 // Plan and upload the k_memo launch of the FGD replicas (before the timed region of a run; cached
 // until events or policies change).
-static int upload_memo(ksim_engine* e, const std::vector<int>& reps, int max_ev);
+static int upload_memo(ksim_engine* e, const PlanInput& in, const std::vector<int>& reps, int max_ev);
 
-static int prepare_memo(ksim_engine* e, int max_ev) {
+static int prepare_memo(ksim_engine* e, const RunEnv& env, int max_ev) {
   if (e->run_mode == 1 || e->run_mode == 2 || e->shard_world > 0) return KSIM_OK;
   std::vector<int> reps, wide, narrow;
   for (int r = 0; r < e->R; ++r)
@@ -2459,87 +2173,165 @@ static int prepare_memo(ksim_engine* e, int max_ev) {
   e->mplan_dirty = false;
   e->mplan_all = reps;
   e->mplan_max_ev = max_ev;
-  e->mplan_ok = false;
-  e->hplan_ok = false;
+  e->memo.ok = false;
+  e->hmemo.ok = false;
   e->split_fgd = false;
-  e->mplan_reps.clear();
-  e->hplan_reps.clear();
+  e->memo.reps.clear();
+  e->hmemo.reps.clear();
   if (reps.empty()) return KSIM_OK;
-  if (e->run_mode == 5) return prepare_hmemo(e, reps, max_ev);  // k_hmemo required
-  if (!e->mplan) e->mplan = std::make_unique<MemoPlan>();
-  MemoPlan& pl = *e->mplan;
+  if (e->run_mode == 5) return prepare_hmemo(e, env, reps, max_ev);  // k_hmemo required
+  MemoPlan& pl = e->memo.plan;
   // run_mode 4 (or KSIM_VARIANT=memo_decider=1 with run_mode 0): the decider variant of k_memo
-  pl.decider = e->run_mode == 4 || (e->run_mode == 0 && variant("memo_decider", 0) == 1);
+  const bool decider = e->run_mode == 4 || (e->run_mode == 0 && env.memo_decider);
   // run_mode 0 with some FGD replicas hinted wide (ksim_engine_set_replica_wgs, the paper sweep's longest chains):
   // those on k_memo, each at its hinted width (the keys in HBM when they do not fit in LDS), the others on k_hmemo at
   // one workgroup each, both groups in one concurrent run (run_persistent)
-  if (e->run_mode == 0 && !wide.empty() && !narrow.empty() && !pl.decider) {
+  if (e->run_mode == 0 && !wide.empty() && !narrow.empty() && !decider) {
     std::vector<int> kr;  // each wide replica at its own hinted width
     for (int r : wide) kr.push_back(e->wgs_hint[r]);
-    if (memo_plan(e, wide, pl, 0, true, &kr)) {
-      int rc = upload_memo(e, wide, max_ev);
+    const PlanInput in = plan_input(e, env, wide);
+    if (memo_plan(in, pl, 0, true, &kr)) {
+      int rc = upload_memo(e, in, wide, max_ev);
       if (rc) return rc;
-      rc = prepare_hmemo(e, narrow, max_ev);
+      rc = prepare_hmemo(e, env, narrow, max_ev);
       if (rc) return rc;
-      if (e->hplan_ok && e->hplan->K == 1) {
+      if (e->hmemo.ok && e->hmemo.plan.K == 1) {
         e->split_fgd = true;
         return KSIM_OK;
       }
-      e->mplan_ok = false;  // no one-workgroup plan for the others: one plan for every FGD replica, below
-      e->mplan_reps.clear();
-      e->hplan_ok = false;
+      e->memo.ok = false;  // no one-workgroup plan for the others: one plan for every FGD replica, below
+      e->memo.reps.clear();
+      e->hmemo.ok = false;
     }
   }
   std::vector<int> kr;  // every FGD replica hinted: each at its width
   if (wide.size() == reps.size())
     for (int r : reps) kr.push_back(e->wgs_hint[r]);
-  if (!memo_plan(e, reps, pl, 0, e->run_mode == 3 || !kr.empty(), kr.empty() ? nullptr : &kr))
-    return e->run_mode == 0 ? prepare_hmemo(e, reps, max_ev) : KSIM_OK;
-  return upload_memo(e, reps, max_ev);
+  const PlanInput in = plan_input(e, env, reps, decider);
+  if (!memo_plan(in, pl, 0, e->run_mode == 3 || !kr.empty(), kr.empty() ? nullptr : &kr))
+    return e->run_mode == 0 ? prepare_hmemo(e, env, reps, max_ev) : KSIM_OK;
+  return upload_memo(e, in, reps, max_ev);
 }
 
-// Upload the k_memo plan of `reps` (memo_plan made it): the per-class tables, the owner code of every event.
-static int upload_memo(ksim_engine* e, const std::vector<int>& reps, int max_ev) {
-  MemoPlan& pl = *e->mplan;
+// Upload the k_memo plan of `reps` (memo_plan made it from `in`): the per-class tables, the owner code of every event.
+static int upload_memo(ksim_engine* e, const PlanInput& in, const std::vector<int>& reps, int max_ev) {
+  MemoPlan& pl = e->memo.plan;
   const int Rg = (int)reps.size();
   int rc;
   const int stride = std::max(max_ev, 1);
-  if ((rc = e->d_win.ensure((size_t)Rg * stride))) return rc;
-  if ((rc = e->d_topg.ensure((size_t)Rg * stride * ksim_memo::kTopWords))) return rc;
-  std::vector<int> evcls((size_t)Rg * stride, -1);
-  for (int gi = 0; gi < Rg; ++gi) {
-    const std::vector<int>& ec = e->h_ev_cls[reps[gi]];
-    for (size_t i = 0; i < ec.size(); ++i) evcls[(size_t)gi * stride + i] = ec[i];
-  }
-  // owner code of every event: workgroup << 16 | first slot of its score group << 8 | slot; -1 delete
-  std::vector<int> evo((size_t)Rg * stride, -1);
-  for (int gi = 0; gi < Rg; ++gi) {
-    const std::vector<int>& ec = e->h_ev_cls[reps[gi]];
-    for (size_t i = 0; i < ec.size(); ++i) {
-      if (ec[i] < 0) continue;
-      const int o = pl.owner[(size_t)gi * pl.Cmax + ec[i]];
-      const int w = o >> 8, slot = o & 0xff;
-      const int ref = pl.wgref[((size_t)pl.wgoff[gi] + w) * pl.Cw + slot];
-      evo[(size_t)gi * stride + i] = (w << 16) | (ref << 8) | slot;
+  if ((rc = e->memo.win.ensure((size_t)Rg * stride))) return rc;
+  if ((rc = e->memo.topg.ensure((size_t)Rg * stride * ksim_memo::kTopWords))) return rc;
+  const MemoEvents t = memo_events(in, pl, stride);
+  hipStream_t st = e->stream;
+  if ((rc = e->memo.evo.upload(t.evo, st))) return rc;
+  if ((rc = e->memo.evcls.upload(t.evcls, st))) return rc;
+  if ((rc = e->memo.pod.upload(pl.pod, st))) return rc;
+  if ((rc = e->memo.owner.upload(pl.owner, st))) return rc;
+  if ((rc = e->memo.wgcls.upload(pl.wgcls, st))) return rc;
+  if ((rc = e->memo.wgref.upload(pl.wgref, st))) return rc;
+  if ((rc = e->memo.wggrp.upload(pl.wggrp, st))) return rc;
+  if ((rc = ensure_score_table(e, st))) return rc;
+  if ((rc = e->memo.wgmap.upload(t.wgmap, st))) return rc;
+  KSIM_HIP(hipStreamSynchronize(st));  // the host vectors are pageable and short-lived
+  if (pl.hkeys && (rc = e->memo.hkeys.ensure((size_t)pl.nwg * pl.Cw * e->N))) return rc;
+  e->memo.reps = reps;
+  e->memo.ok = true;
+  return KSIM_OK;
+}
+
+// KSIM_PROFILE=2: the step trace of the launch just enqueued (d_trace: kTrace words per workgroup and each of the first
+// TS steps).
+static int print_memo_trace(ksim_engine* e, const MemoPlan& pl, DevBuf<unsigned long long>& d_trace, int TS, hipStream_t st) {
+  constexpr int kT = ksim_memo::kTrace;
+  // per step: owner's start -> publish, publish -> each other workgroup's receive, receive -> start
+  // (s_memrealtime, 100 MHz); replica 0 only
+  KSIM_HIP(hipStreamSynchronize(st));
+  const int K = pl.Kr[0];
+  std::vector<unsigned long long> h((size_t)kT * pl.nwg * TS);
+  KSIM_HIP(hipMemcpy(h.data(), d_trace.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
+  d_trace.release();
+  std::vector<int> evo((size_t)TS);
+  KSIM_HIP(hipMemcpy(evo.data(), e->memo.evo.p, sizeof(int) * TS, hipMemcpyDeviceToHost));
+  auto at = [&](int w, int s, int k) { return (double)h[((size_t)w * TS + s) * kT + k]; };
+  double crit = 0, hand = 0, hmax = 0, period = 0, lag = 0, f0 = 0, spin = 0, nhand = 0;
+  int nc = 0, nh = 0, nf = 0, nn = 0;
+  for (int s = 1; s + 1 < TS; ++s) {
+    if (evo[s] < 0 || evo[s + 1] < 0) continue;
+    const int o = evo[s] >> 16, o2 = evo[s + 1] >> 16;
+    crit += at(o, s, 1) - at(o, s, 0);
+    if (at(o, s, 2) > 0 && at(o, s, 3) > 0) {
+      f0 += at(o, s, 3) - at(o, s, 0);   // start -> all critical F done
+      spin += at(o, s, 2) - at(o, s, 3); // -> fresh key known
+      ++nf;
+    }
+    period += at(o2, s + 1, 1) - at(o, s, 1);
+    if (o2 != o) lag += at(o2, s + 1, 0) - at(o2, s, 1);  // next owner: receive s -> start s+1
+    if (o2 != o) {  // the hand-off the chain goes through: the next owner's own receive, not the mean of all
+      nhand += at(o2, s, 1) - at(o, s, 1);
+      ++nn;
+    }
+    ++nc;
+    for (int w = 0; w < K; ++w) {
+      if (w == o) continue;
+      const double d = at(w, s, 1) - at(o, s, 1);
+      hand += d;
+      hmax = std::max(hmax, d);
+      ++nh;
     }
   }
-  hipStream_t st = e->stream;
-  if ((rc = e->d_m_evo.upload(evo, st))) return rc;
-  if ((rc = e->d_m_evcls.upload(evcls, st))) return rc;
-  if ((rc = e->d_m_pod.upload(pl.pod, st))) return rc;
-  if ((rc = e->d_m_owner.upload(pl.owner, st))) return rc;
-  if ((rc = e->d_m_wgcls.upload(pl.wgcls, st))) return rc;
-  if ((rc = e->d_m_wgref.upload(pl.wgref, st))) return rc;
-  if ((rc = e->d_m_wggrp.upload(pl.wggrp, st))) return rc;
-  if ((rc = ensure_score_table(e, st))) return rc;
-  std::vector<int> wgmap((size_t)pl.nwg);
-  for (int gi = 0; gi < Rg; ++gi)
-    for (int w = 0; w < pl.Kr[gi]; ++w) wgmap[(size_t)pl.wgoff[gi] + w] = (gi << 8) | w;
-  if ((rc = e->d_m_wgmap.upload(wgmap, st))) return rc;
-  KSIM_HIP(hipStreamSynchronize(st));  // the host vectors are pageable and short-lived
-  if (pl.hkeys && (rc = e->d_m_hkeys.ensure((size_t)pl.nwg * pl.Cw * e->N))) return rc;
-  e->mplan_reps = reps;
-  e->mplan_ok = true;
+  if (nc && nh)
+    std::fprintf(stderr, "ksim memo trace (replica 0, %d steps, us): owner start->publish %.3f; publish->receive mean %.3f max %.3f; "
+                 "next owner receive->start %.3f; publish->publish %.3f; owner start->all F done %.3f, ->fresh key %.3f; "
+                 "next owner publish->receive %.3f (%d of %d steps hand over)\n",
+                 TS, crit / nc / 100, hand / nh / 100, hmax / 100, lag / nc / 100, period / nc / 100,
+                 nf ? f0 / nf / 100 : 0.0, nf ? (f0 + spin) / nf / 100 : 0.0, nn ? nhand / nn / 100 : 0.0, nn, nc);
+  return KSIM_OK;
+}
+
+// KSIM_PROFILE=1: the phase table of the launch just enqueued (d_prof).
+static int print_memo_profile(ksim_engine* e, const MemoPlan& pl, int Rg, int max_ev, hipStream_t st) {
+  KSIM_HIP(hipStreamSynchronize(st));
+  const int nb = pl.nwg, P = ksim_memo::kProfPhases;
+  std::vector<unsigned long long> h((size_t)nb * P);
+  KSIM_HIP(hipMemcpy(h.data(), e->d_prof.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
+  static const char* names[] = {"init", "A:crit-F+list", "syncA", "B:publish", "B:eval", "syncB", "C:keys", "top2",
+                                "poll+bind", "end-sync"};
+  std::fprintf(stderr, "ksim memo profile: %d workgroups (K=%d Cw=%d nfw=%d), %d steps; us/step mean [max]:", nb, pl.K,
+               pl.Cw, pl.nfw, max_ev);
+  double init = 0;
+  for (int b = 0; b < nb; ++b) init += (double)h[(size_t)b * P] / 1e5;
+  std::fprintf(stderr, " (init %.3f ms)", init / nb);
+  for (int ph = 1; ph < 10; ++ph) {
+    double sum = 0, mx = 0;
+    for (int b = 0; b < nb; ++b) {
+      const double us = (double)h[(size_t)b * P + ph] / 100.0 / std::max(max_ev, 1);
+      sum += us;
+      mx = std::max(mx, us);
+    }
+    std::fprintf(stderr, " %s %.3f [%.3f];", names[ph], sum / nb, mx);
+  }
+  double cyc = 0, tick = 0;
+  for (int b = 0; b < nb; ++b) { cyc += (double)h[(size_t)b * P + 10]; tick += (double)h[(size_t)b * P + 11]; }
+  for (int ph = 12; ph < 21; ++ph) {
+    double sum = 0;
+    for (int b = 0; b < nb; ++b) sum += (double)h[(size_t)b * P + ph] / 100.0 / std::max(max_ev, 1);
+    static const char* extra[] = {"listwave-A", "listwave-C", "step-start loads", "owner A per step",
+                                  "owner: prefetch done", "crit F all done", "keys", "result written",
+                                  "granule stored"};
+    // owner phases: summed over the K workgroups of a replica (one owner per step)
+    std::fprintf(stderr, " %s %.3f;", extra[ph - 12], ph >= 15 ? sum / std::max(Rg, 1) : sum / nb);
+  }
+  if (pl.decider) {  // the deciders' own phases (workgroup 0 of each replica)
+    static const char* dn[] = {"list + top wait", "F", "decide + bind", "end barrier"};
+    std::fprintf(stderr, " | decider:");
+    for (int ph = 20; ph < 24; ++ph) {
+      double sum = 0;
+      for (int b = 0; b < nb; b += pl.K) sum += (double)h[(size_t)b * P + ph] / 100.0 / std::max(max_ev, 1);
+      std::fprintf(stderr, " %s %.3f;", dn[ph - 20], sum / std::max(nb / pl.K, 1));
+    }
+  }
+  if (tick > 0) std::fprintf(stderr, " shader clock %.0f MHz, wall %.3f ms", cyc / tick * 100.0, tick / nb / 1e5);
+  std::fprintf(stderr, "\n");
   return KSIM_OK;
 }
 
@@ -2550,35 +2342,35 @@ static int launch_memo(ksim_engine* e, const RunEnv& env, const MemoPlan& pl, in
                        int* started = nullptr, int gate_epoch = 0) {
   int rc;
   const int stride = std::max(max_ev, 1);
-  KSIM_HIP(hipMemsetAsync(e->d_win.p, 0, sizeof(unsigned) * (size_t)Rg * stride, st));
+  KSIM_HIP(hipMemsetAsync(e->memo.win.p, 0, sizeof(unsigned) * (size_t)Rg * stride, st));
   if (pl.decider)
-    KSIM_HIP(hipMemsetAsync(e->d_topg.p, 0, sizeof(unsigned) * (size_t)Rg * stride * ksim_memo::kTopWords, st));
+    KSIM_HIP(hipMemsetAsync(e->memo.topg.p, 0, sizeof(unsigned) * (size_t)Rg * stride * ksim_memo::kTopWords, st));
   ksim_memo::MemoArgs ma;
   ma.reps = e->d_reps.p;
   ma.rep_list = e->d_replist.p + first;
-  ma.wg_map = e->d_m_wgmap.p;
+  ma.wg_map = e->memo.wgmap.p;
   ma.N = e->N;
   ma.K = pl.K;
   ma.Cw = pl.Cw;
   ma.nfw = pl.nfw;
   ma.Cmax = pl.Cmax;
-  ma.cls_pod = e->d_m_pod.p;
-  ma.cls_owner = e->d_m_owner.p;
-  ma.wg_cls = e->d_m_wgcls.p;
-  ma.wg_ref = e->d_m_wgref.p;
-  ma.wg_grp = e->d_m_wggrp.p;
-  ma.ev_owner = e->d_m_evo.p;
+  ma.cls_pod = e->memo.pod.p;
+  ma.cls_owner = e->memo.owner.p;
+  ma.wg_cls = e->memo.wgcls.p;
+  ma.wg_ref = e->memo.wgref.p;
+  ma.wg_grp = e->memo.wggrp.p;
+  ma.ev_owner = e->memo.evo.p;
   ma.th = e->d_th.p;
-  ma.win = e->d_win.p;
+  ma.win = e->memo.win.p;
   ma.win_stride = stride;
   ma.fail = e->d_fail.p;
   ma.prof = nullptr;
   ma.trace = nullptr;
   ma.trace_steps = 0;
   ma.decider = pl.decider ? 1 : 0;
-  ma.ev_cls = e->d_m_evcls.p;
-  ma.topg = e->d_topg.p;
-  ma.hkeys = pl.hkeys ? e->d_m_hkeys.p : nullptr;
+  ma.ev_cls = e->memo.evcls.p;
+  ma.topg = e->memo.topg.p;
+  ma.hkeys = pl.hkeys ? e->memo.hkeys.p : nullptr;
   ma.started = started;
   ma.gate_epoch = gate_epoch;
   ma.skip = env.skip;
@@ -2587,9 +2379,8 @@ static int launch_memo(ksim_engine* e, const RunEnv& env, const MemoPlan& pl, in
   const bool tracing = env.profile == 2;
   DevBuf<unsigned long long> d_trace;
   const int TS = std::min(max_ev, 4000);
-  constexpr int kT = ksim_memo::kTrace;
   if (tracing) {
-    if ((rc = d_trace.alloc(kT * (size_t)pl.nwg * TS))) return rc;
+    if ((rc = d_trace.alloc(ksim_memo::kTrace * (size_t)pl.nwg * TS))) return rc;
     if ((rc = d_trace.zero(st))) return rc;
     ma.trace = d_trace.p;
     ma.trace_steps = TS;
@@ -2599,113 +2390,17 @@ static int launch_memo(ksim_engine* e, const RunEnv& env, const MemoPlan& pl, in
     KSIM_HIP(hipMemsetAsync(e->d_prof.p, 0, sizeof(unsigned long long) * (size_t)pl.nwg * ksim_memo::kProfPhases, st));
     ma.prof = e->d_prof.p;
   }
-  // the general instantiation for the profile / trace / deletes / no score table, else the lean one (with the
-  // report's stores when the report is on)
-  const bool general = profile || tracing || !e->d_th.p ||
-                       std::any_of(e->mplan_reps.begin(), e->mplan_reps.end(), [&](int r) { return (bool)e->has_delete[r]; });
-  // the hdelay test knob: the lean kernel with the stress delays compiled in (or the general one, which has them)
-  using ksim_memo::k_memo;
-  const void* f = pl.decider ? (const void*)k_memo<true, true>
-                  : pl.hkeys ? (general ? (const void*)k_memo<false, true, false, false, true>
-                                        : e->report ? (const void*)k_memo<false, false, false, true, true>
-                                                    : (const void*)k_memo<false, false, false, false, true>)
-                  : general ? (const void*)k_memo<false, true>
-                  : ma.delay ? (const void*)k_memo<false, false, true>
-                  : e->report ? (const void*)k_memo<false, false, false, true> : (const void*)k_memo<false, false>;
+  const bool any_delete = std::any_of(e->memo.reps.begin(), e->memo.reps.end(), [&](int r) { return (bool)e->has_delete[r]; });
+  const void* f = memo_kernel(memo_form(pl.decider, pl.hkeys, profile, tracing, e->d_th.p != nullptr, any_delete, e->report,
+                                        ma.delay));
   const TypDev* tpp = e->d_tp.p;
   rc = launch_persistent(f, pl.nwg, ksim_memo::kMBlock, pl.lds, st, e->coop && pl.K > 1 && !started, ma, tpp);
   if (rc) return rc;
   hipLaunchKernelGGL(ksim_memo::k_memo_finish, dim3((unsigned)((stride + 255) / 256), (unsigned)Rg), dim3(256), 0, st,
                      e->d_reps.p, (const int*)(e->d_replist.p + first), e->N);
   KSIM_HIP(hipGetLastError());
-  if (tracing) {
-    // per step: owner's start -> publish, publish -> each other workgroup's receive, receive -> start
-    // (s_memrealtime, 100 MHz); replica 0 only
-    KSIM_HIP(hipStreamSynchronize(st));
-    const int K = pl.Kr[0];
-    std::vector<unsigned long long> h((size_t)kT * pl.nwg * TS);
-    KSIM_HIP(hipMemcpy(h.data(), d_trace.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
-    d_trace.release();
-    std::vector<int> evo((size_t)TS);
-    KSIM_HIP(hipMemcpy(evo.data(), e->d_m_evo.p, sizeof(int) * TS, hipMemcpyDeviceToHost));
-    auto at = [&](int w, int s, int k) { return (double)h[((size_t)w * TS + s) * kT + k]; };
-    double crit = 0, hand = 0, hmax = 0, period = 0, lag = 0, f0 = 0, spin = 0, nhand = 0;
-    int nc = 0, nh = 0, nf = 0, nn = 0;
-    for (int s = 1; s + 1 < TS; ++s) {
-      if (evo[s] < 0 || evo[s + 1] < 0) continue;
-      const int o = evo[s] >> 16, o2 = evo[s + 1] >> 16;
-      crit += at(o, s, 1) - at(o, s, 0);
-      if (at(o, s, 2) > 0 && at(o, s, 3) > 0) {
-        f0 += at(o, s, 3) - at(o, s, 0);   // start -> all critical F done
-        spin += at(o, s, 2) - at(o, s, 3); // -> fresh key known
-        ++nf;
-      }
-      period += at(o2, s + 1, 1) - at(o, s, 1);
-      if (o2 != o) lag += at(o2, s + 1, 0) - at(o2, s, 1);  // next owner: receive s -> start s+1
-      if (o2 != o) {  // the hand-off the chain goes through: the next owner's own receive, not the mean of all
-        nhand += at(o2, s, 1) - at(o, s, 1);
-        ++nn;
-      }
-      ++nc;
-      for (int w = 0; w < K; ++w) {
-        if (w == o) continue;
-        const double d = at(w, s, 1) - at(o, s, 1);
-        hand += d;
-        hmax = std::max(hmax, d);
-        ++nh;
-      }
-    }
-    if (nc && nh)
-      std::fprintf(stderr, "ksim memo trace (replica 0, %d steps, us): owner start->publish %.3f; publish->receive mean %.3f max %.3f; "
-                   "next owner receive->start %.3f; publish->publish %.3f; owner start->all F done %.3f, ->fresh key %.3f; "
-                   "next owner publish->receive %.3f (%d of %d steps hand over)\n",
-                   TS, crit / nc / 100, hand / nh / 100, hmax / 100, lag / nc / 100, period / nc / 100,
-                   nf ? f0 / nf / 100 : 0.0, nf ? (f0 + spin) / nf / 100 : 0.0, nn ? nhand / nn / 100 : 0.0, nn, nc);
-  }
-  if (profile) {
-    KSIM_HIP(hipStreamSynchronize(st));
-    const int nb = pl.nwg, P = ksim_memo::kProfPhases;
-    std::vector<unsigned long long> h((size_t)nb * P);
-    KSIM_HIP(hipMemcpy(h.data(), e->d_prof.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
-    static const char* names[] = {"init", "A:crit-F+list", "syncA", "B:publish", "B:eval", "syncB", "C:keys", "top2",
-                                  "poll+bind", "end-sync"};
-    std::fprintf(stderr, "ksim memo profile: %d workgroups (K=%d Cw=%d nfw=%d), %d steps; us/step mean [max]:", nb, pl.K,
-                 pl.Cw, pl.nfw, max_ev);
-    double init = 0;
-    for (int b = 0; b < nb; ++b) init += (double)h[(size_t)b * P] / 1e5;
-    std::fprintf(stderr, " (init %.3f ms)", init / nb);
-    for (int ph = 1; ph < 10; ++ph) {
-      double sum = 0, mx = 0;
-      for (int b = 0; b < nb; ++b) {
-        const double us = (double)h[(size_t)b * P + ph] / 100.0 / std::max(max_ev, 1);
-        sum += us;
-        mx = std::max(mx, us);
-      }
-      std::fprintf(stderr, " %s %.3f [%.3f];", names[ph], sum / nb, mx);
-    }
-    double cyc = 0, tick = 0;
-    for (int b = 0; b < nb; ++b) { cyc += (double)h[(size_t)b * P + 10]; tick += (double)h[(size_t)b * P + 11]; }
-    for (int ph = 12; ph < 21; ++ph) {
-      double sum = 0;
-      for (int b = 0; b < nb; ++b) sum += (double)h[(size_t)b * P + ph] / 100.0 / std::max(max_ev, 1);
-      static const char* extra[] = {"listwave-A", "listwave-C", "step-start loads", "owner A per step",
-                                    "owner: prefetch done", "crit F all done", "keys", "result written",
-                                    "granule stored"};
-      // owner phases: summed over the K workgroups of a replica (one owner per step)
-      std::fprintf(stderr, " %s %.3f;", extra[ph - 12], ph >= 15 ? sum / std::max(Rg, 1) : sum / nb);
-    }
-    if (pl.decider) {  // the deciders' own phases (workgroup 0 of each replica)
-      static const char* dn[] = {"list + top wait", "F", "decide + bind", "end barrier"};
-      std::fprintf(stderr, " | decider:");
-      for (int ph = 20; ph < 24; ++ph) {
-        double sum = 0;
-        for (int b = 0; b < nb; b += pl.K) sum += (double)h[(size_t)b * P + ph] / 100.0 / std::max(max_ev, 1);
-        std::fprintf(stderr, " %s %.3f;", dn[ph - 20], sum / std::max(nb / pl.K, 1));
-      }
-    }
-    if (tick > 0) std::fprintf(stderr, " shader clock %.0f MHz, wall %.3f ms", cyc / tick * 100.0, tick / nb / 1e5);
-    std::fprintf(stderr, "\n");
-  }
+  if (tracing && (rc = print_memo_trace(e, pl, d_trace, TS, st))) return rc;
+  if (profile && (rc = print_memo_profile(e, pl, Rg, max_ev, st))) return rc;
   return KSIM_OK;
 }
 
@@ -2713,7 +2408,7 @@ static int launch_memo(ksim_engine* e, const RunEnv& env, const MemoPlan& pl, in
 // node-sharded engine's first global rank.
 static int hmemo_init_keys(ksim_engine* e, int Rg, int first, hipStream_t st, int roff) {
   using namespace ksim_hmemo;
-  const HPlan& pl = *e->hplan;
+  const HPlan& pl = e->hmemo.plan;
   HInitArgs ia;
   ia.roff = roff;
   ia.reps = e->d_reps.p;
@@ -2724,28 +2419,28 @@ static int hmemo_init_keys(ksim_engine* e, int Rg, int first, hipStream_t st, in
   ia.Cmax = pl.Cmax;
   ia.Gmax = pl.Gmax;
   ia.Smax = pl.Smax;
-  ia.cg = e->d_h_cg.p;
-  ia.cls = e->d_h_cls.p;
-  ia.cgrp = e->d_h_cgrp.p;
-  ia.gpod = e->d_h_gpod.p;
-  ia.st = e->d_h_st.p;
-  ia.ns = e->d_h_ns.p;
-  ia.nstate = e->d_h_nstate.p;
-  ia.gsc = e->d_h_gsc.p;
-  ia.keys = e->d_h_keys.p;
-  ia.l1 = e->d_h_l1.p;
-  ia.l2 = pl.l2 ? e->d_h_l2.p : nullptr;
-  ia.cnt = e->d_h_cnt.p;
+  ia.cg = e->hmemo.cg.p;
+  ia.cls = e->hmemo.cls.p;
+  ia.cgrp = e->hmemo.cgrp.p;
+  ia.gpod = e->hmemo.gpod.p;
+  ia.st = e->hmemo.st.p;
+  ia.ns = e->hmemo.ns.p;
+  ia.nstate = e->hmemo.nstate.p;
+  ia.gsc = e->hmemo.gsc.p;
+  ia.keys = e->hmemo.keys.p;
+  ia.l1 = e->hmemo.l1.p;
+  ia.l2 = pl.l2 ? e->hmemo.l2.p : nullptr;
+  ia.cnt = e->hmemo.cnt.p;
   ia.th = e->d_th.p;
-  ia.mtoff = pl.Mtab > 0 ? e->d_h_mtoff.p : nullptr;
-  ia.na = pl.Mtab > 0 ? e->d_h_na.p : nullptr;
+  ia.mtoff = pl.Mtab > 0 ? e->hmemo.mtoff.p : nullptr;
+  ia.na = pl.Mtab > 0 ? e->hmemo.na.p : nullptr;
   ia.Mslots = pl.Mslots;
   if (pl.Mtab > 0) {
     hipLaunchKernelGGL(k_hinit_na, dim3((unsigned)((kNaStride + 255) / 256), (unsigned)pl.Mslots, (unsigned)Rg), dim3(256), 0,
                        st, ia, (const TypDev*)e->d_tp.p);
     KSIM_HIP(hipGetLastError());
   }
-  KSIM_HIP(hipMemsetAsync(e->d_h_cnt.p, 0, sizeof(int) * (size_t)Rg * pl.Cmax, st));
+  KSIM_HIP(hipMemsetAsync(e->hmemo.cnt.p, 0, sizeof(int) * (size_t)Rg * pl.Cmax, st));
   hipLaunchKernelGGL(k_hinit_gk, dim3((unsigned)((pl.Smax + 255) / 256), (unsigned)pl.Gmax, (unsigned)Rg), dim3(256), 0,
                      st, ia, (const TypDev*)e->d_tp.p);
   KSIM_HIP(hipGetLastError());
@@ -2760,31 +2455,31 @@ static bool dead_skip(const ksim_engine* e, const RunEnv& env, const std::vector
 // k_hmemo's arguments for the planned launch (one group of Rg replicas from d_replist + first).
 static ksim_hmemo::HMemoArgs hmemo_args(ksim_engine* e, const RunEnv& env, int first, int stride) {
   using namespace ksim_hmemo;
-  const HPlan& pl = *e->hplan;
+  const HPlan& pl = e->hmemo.plan;
   HMemoArgs ma;
   std::memset(&ma, 0, sizeof ma);  // every field a caller does not set (the gate, profile, exchange pointers) is null
   ma.reps = e->d_reps.p;
   ma.rep_list = e->d_replist.p + first;
   ma.Mtab = pl.Mtab;
   ma.Mslots = pl.Mslots;
-  ma.mtoff = pl.Mtab > 0 ? e->d_h_mtoff.p : nullptr;
-  ma.mtab = pl.Mtab > 0 ? e->d_h_mtab.p : nullptr;
-  ma.na = pl.Mtab > 0 ? e->d_h_na.p : nullptr;
+  ma.mtoff = pl.Mtab > 0 ? e->hmemo.mtoff.p : nullptr;
+  ma.mtab = pl.Mtab > 0 ? e->hmemo.mtab.p : nullptr;
+  ma.na = pl.Mtab > 0 ? e->hmemo.na.p : nullptr;
   ma.N = e->N;
   ma.Npad = pl.Npad;
   ma.nb = pl.nb;
   ma.Cmax = pl.Cmax;
   ma.Gmax = pl.Gmax;
-  ma.cg = e->d_h_cg.p;
-  ma.cls = e->d_h_cls.p;
-  ma.cgrp = e->d_h_cgrp.p;
-  ma.gpod = e->d_h_gpod.p;
-  ma.evc = e->d_h_evc.p;
+  ma.cg = e->hmemo.cg.p;
+  ma.cls = e->hmemo.cls.p;
+  ma.cgrp = e->hmemo.cgrp.p;
+  ma.gpod = e->hmemo.gpod.p;
+  ma.evc = e->hmemo.evc.p;
   ma.stride = stride;
-  ma.keys = e->d_h_keys.p;
-  ma.l1 = e->d_h_l1.p;
-  ma.l2 = pl.l2 ? e->d_h_l2.p : nullptr;
-  ma.cnt0 = e->d_h_cnt.p;
+  ma.keys = e->hmemo.keys.p;
+  ma.l1 = e->hmemo.l1.p;
+  ma.l2 = pl.l2 ? e->hmemo.l2.p : nullptr;
+  ma.cnt0 = e->hmemo.cnt.p;
   ma.th = e->d_th.p;
   ma.prof = nullptr;
   ma.K = pl.K;
@@ -2804,17 +2499,54 @@ static ksim_hmemo::HMemoArgs hmemo_args(ksim_engine* e, const RunEnv& env, int f
     std::iota(all.begin(), all.end(), 0);
     ma.skip = dead_skip(e, env, all) ? 1 : 0;
   }
-  {  // KSIM_VARIANT hpf (one workgroup per replica): 1 = wave 0 lists the next refresh (the default since r04: C4 190.7 ->
-     // 178-185 ms, C2 run_mode 5 50.3 -> 47.7 ms, profiles/r04/memo/ab_runs.txt), 2 = touches its flagged rows, 0 = off
-    ma.pf = (int)variant("hpf", 1) & 7;  // (4: the wide form lists on wave 0 too)
-  }
+  ma.pf = env.hpf;
   ma.delay = env.hdelay;
-  {  // KSIM_VARIANT hprune (A/B): the F list's group pruning for replicas with more than this many typical pods
-    // (-1: every replica; default 64: the large typed tables, where the F rounds bound the step)
-    ma.prune_t = (int)variant("hprune", 64);
-  }
+  ma.prune_t = env.hprune;
   for (int q = 0; q < kMaxPeers; ++q) ma.peer[q] = nullptr;
   return ma;
+}
+
+// KSIM_PROFILE=1: the phase table of the k_hmemo launch just enqueued (hmemo.prof).
+static int print_hmemo_profile(ksim_engine* e, const HPlan& pl, int Rg, int max_ev, hipStream_t st) {
+  using namespace ksim_hmemo;
+  // per workgroup phase sums; refresh phases 0-4 run on one workgroup per step (the owner of the
+  // changed node), so they are summed over a replica's workgroups, phase 5 is averaged over them
+  KSIM_HIP(hipStreamSynchronize(st));
+  const int nwg = Rg * pl.K;
+  std::vector<unsigned long long> h((size_t)nwg * kHProf);
+  KSIM_HIP(hipMemcpy(h.data(), e->hmemo.prof.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
+  // waves 1-15 (the bulk: every class but the event's own): 0 + 2 on the F waves, 4 on the class
+  // waves beside them, then 3; wave 0: 1 (the own class's refresh, the critical path), 5 (the rest of
+  // its step: decide + Bind, then the end-of-step barrier)
+  static const char* names[] = {"bulk: list (wave 1)", "critical own-class refresh", "bulk: F (F waves)",
+                                 "bulk: join + class update", "class waves: class pass + flagged blocks",
+                                 "wave 0 decide+bind+wait"};
+  std::fprintf(stderr, "ksim hmemo profile: %d replicas x K=%d (S %d), LDS %zu B, Cmax %d Gmax %d Smax %d; us/step mean [max]:",
+               Rg, pl.K, pl.S, pl.lds, pl.Cmax, pl.Gmax, pl.Smax);
+  const double steps = std::max(max_ev, 1);
+  for (int ph = 0; ph < 6; ++ph) {
+    double sum = 0, mx = 0;
+    for (int g = 0; g < Rg; ++g) {
+      double us = 0;
+      for (int k = 0; k < pl.K; ++k) us += (double)h[((size_t)g * pl.K + k) * kHProf + ph] / 100.0 / steps;
+      if (ph == 5) us /= pl.K;
+      sum += us;
+      mx = std::max(mx, us);
+    }
+    std::fprintf(stderr, " %s %.3f [%.3f];", names[ph], sum / Rg, mx);
+  }
+  double it = 0, fl = 0, rs = 0, cyc = 0, tick = 0;
+  for (int b = 0; b < nwg; ++b) {
+    it += (double)h[(size_t)b * kHProf + 7];
+    fl += (double)h[(size_t)b * kHProf + 8];
+    rs += (double)h[(size_t)b * kHProf + 9];
+    cyc += (double)h[(size_t)b * kHProf + 10];
+    tick += (double)h[(size_t)b * kHProf + 11];
+  }
+  if (rs > 0) std::fprintf(stderr, " F items/refresh %.1f, flagged classes/refresh %.1f;", it / rs, fl / rs);
+  if (tick > 0) std::fprintf(stderr, " shader clock %.0f MHz, wall %.3f ms", cyc / tick * 100.0, tick / nwg / 1e5);
+  std::fprintf(stderr, "\n");
+  return KSIM_OK;
 }
 
 // started: the residency gate's flags (K = 1 only); *gated tells the caller whether the launch carries them --
@@ -2822,7 +2554,7 @@ static ksim_hmemo::HMemoArgs hmemo_args(ksim_engine* e, const RunEnv& env, int f
 static int launch_hmemo(ksim_engine* e, const RunEnv& env, int Rg, int first, int max_ev, hipStream_t st,
                         int* started = nullptr, int gate_epoch = 0, bool* gated = nullptr) {
   using namespace ksim_hmemo;
-  const HPlan& pl = *e->hplan;
+  const HPlan& pl = e->hmemo.plan;
   const int stride = std::max(max_ev, 1);
   int irc = hmemo_init_keys(e, Rg, first, st, 0);
   if (irc) return irc;
@@ -2831,31 +2563,27 @@ static int launch_hmemo(ksim_engine* e, const RunEnv& env, int Rg, int first, in
   ma.gate_epoch = gate_epoch;
   if (gated) *gated = false;
   bool any_delete = false;
-  for (const int r : e->hplan_reps) any_delete = any_delete || e->has_delete[r];  // the FGD replicas
+  for (const int r : e->hmemo.reps) any_delete = any_delete || e->has_delete[r];  // the FGD replicas
   if (pl.K > 1) {
     if (any_delete) {
-      int rc = e->d_h_hist.ensure((size_t)Rg * pl.K * stride);
+      int rc = e->hmemo.hist.ensure((size_t)Rg * pl.K * stride);
       if (rc) return rc;
-      ma.hist = e->d_h_hist.p;
+      ma.hist = e->hmemo.hist.p;
     }
     KSIM_HIP(hipMemsetAsync(e->d_gran.p, 0, sizeof(unsigned long long) * (size_t)Rg * 2 * pl.K * 2, st));
   }
   const bool profile = env.timers();
   if (profile) {
-    int rc = e->d_h_prof.ensure((size_t)Rg * pl.K * kHProf);
+    int rc = e->hmemo.prof.ensure((size_t)Rg * pl.K * kHProf);
     if (rc) return rc;
-    KSIM_HIP(hipMemsetAsync(e->d_h_prof.p, 0, sizeof(unsigned long long) * (size_t)Rg * pl.K * kHProf, st));
-    ma.prof = e->d_h_prof.p;
+    KSIM_HIP(hipMemsetAsync(e->hmemo.prof.p, 0, sizeof(unsigned long long) * (size_t)Rg * pl.K * kHProf, st));
+    ma.prof = e->hmemo.prof.p;
   }
-  const bool gen = profile || ma.delay != 0;  // the general instantiation: timers, stress delays
   // the large-table instantiations (per-model tables of typed replicas, the F-list pruning) when a replica of
   // the launch has use for them
   bool model = pl.Mtab > 0;
-  for (const int r : e->hplan_reps) model = model || e->reps[r].nt > ma.prune_t;  // the FGD replicas
-  const void* f = pl.K == 1 ? (gen ? (model ? (const void*)k_hmemo<0, true, true> : (const void*)k_hmemo<0, true>)
-                                   : (model ? (const void*)k_hmemo<0, false, true> : (const void*)k_hmemo<0, false>))
-                  : pl.K <= 64 ? (gen ? (const void*)k_hmemo<1, true> : (const void*)k_hmemo<1, false>)
-                               : (gen ? (const void*)k_hmemo<4, true> : (const void*)k_hmemo<4, false>);
+  for (const int r : e->hmemo.reps) model = model || e->reps[r].nt > ma.prune_t;  // the FGD replicas
+  const void* f = hmemo_kernel(hmemo_form(kHLocal, pl.K, profile, ma.delay, model));
   if (pl.K > 1 && Rg * pl.K > resident_cap(e, f, pl.lds)) {
     std::fprintf(stderr, "ksim: k_hmemo needs %d co-resident workgroups\n", Rg * pl.K);
     return KSIM_ERANGE;
@@ -2868,45 +2596,7 @@ static int launch_hmemo(ksim_engine* e, const RunEnv& env, int Rg, int first, in
   hipLaunchKernelGGL(ksim_memo::k_memo_finish, dim3((unsigned)((stride + 255) / 256), (unsigned)Rg), dim3(256), 0, st,
                      e->d_reps.p, (const int*)(e->d_replist.p + first), e->N);
   KSIM_HIP(hipGetLastError());
-  if (profile) {
-    // per workgroup phase sums; refresh phases 0-4 run on one workgroup per step (the owner of the
-    // changed node), so they are summed over a replica's workgroups, phase 5 is averaged over them
-    KSIM_HIP(hipStreamSynchronize(st));
-    const int nwg = Rg * pl.K;
-    std::vector<unsigned long long> h((size_t)nwg * kHProf);
-    KSIM_HIP(hipMemcpy(h.data(), e->d_h_prof.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
-    // waves 1-15 (the bulk: every class but the event's own): 0 + 2 on the F waves, 4 on the class
-    // waves beside them, then 3; wave 0: 1 (the own class's refresh, the critical path), 5 (the rest of
-    // its step: decide + Bind, then the end-of-step barrier)
-    static const char* names[] = {"bulk: list (wave 1)", "critical own-class refresh", "bulk: F (F waves)",
-                                   "bulk: join + class update", "class waves: class pass + flagged blocks",
-                                   "wave 0 decide+bind+wait"};
-    std::fprintf(stderr, "ksim hmemo profile: %d replicas x K=%d (S %d), LDS %zu B, Cmax %d Gmax %d Smax %d; us/step mean [max]:",
-                 Rg, pl.K, pl.S, pl.lds, pl.Cmax, pl.Gmax, pl.Smax);
-    const double steps = std::max(max_ev, 1);
-    for (int ph = 0; ph < 6; ++ph) {
-      double sum = 0, mx = 0;
-      for (int g = 0; g < Rg; ++g) {
-        double us = 0;
-        for (int k = 0; k < pl.K; ++k) us += (double)h[((size_t)g * pl.K + k) * kHProf + ph] / 100.0 / steps;
-        if (ph == 5) us /= pl.K;
-        sum += us;
-        mx = std::max(mx, us);
-      }
-      std::fprintf(stderr, " %s %.3f [%.3f];", names[ph], sum / Rg, mx);
-    }
-    double it = 0, fl = 0, rs = 0, cyc = 0, tick = 0;
-    for (int b = 0; b < nwg; ++b) {
-      it += (double)h[(size_t)b * kHProf + 7];
-      fl += (double)h[(size_t)b * kHProf + 8];
-      rs += (double)h[(size_t)b * kHProf + 9];
-      cyc += (double)h[(size_t)b * kHProf + 10];
-      tick += (double)h[(size_t)b * kHProf + 11];
-    }
-    if (rs > 0) std::fprintf(stderr, " F items/refresh %.1f, flagged classes/refresh %.1f;", it / rs, fl / rs);
-    if (tick > 0) std::fprintf(stderr, " shader clock %.0f MHz, wall %.3f ms", cyc / tick * 100.0, tick / nwg / 1e5);
-    std::fprintf(stderr, "\n");
-  }
+  if (profile) return print_hmemo_profile(e, pl, Rg, max_ev, st);
   return KSIM_OK;
 }
 
@@ -3057,28 +2747,6 @@ ksim_engine::~ksim_engine() {
 }
 
 void ksim_engine_destroy(ksim_engine* e) { if (e) delete e; }
-
-static int to_pod_dev(const ksim_pod& s, PodDev* d) {
-  if (s.gpu_milli < 0 || s.gpu_milli > kMilli || s.gpu_count < 0 || s.gpu_count > kMaxGpu) return KSIM_ERANGE;
-  if (s.cpu_milli < 0 || s.cpu_milli > 0x3fffffff || s.cpu_nz_milli < 0 || s.cpu_nz_milli > 0x3fffffff ||
-      s.mem_mib < 0 || s.mem_mib > 0x3fffffff)
-    return KSIM_ERANGE;
-  std::memset(d, 0, sizeof *d);
-  d->cpu_req = (int32_t)s.cpu_milli;
-  d->cpu_nz = (int32_t)s.cpu_nz_milli;
-  d->mem = (int32_t)s.mem_mib;
-  d->milli = (int16_t)s.gpu_milli;
-  d->num = (int8_t)s.gpu_count;
-  // GetGpuAffinityFromPodAnnotation (open-gpu-share/utils/pod.go:111-123)
-  if (s.gpu_count == 0) d->tag = -1;
-  else if (s.gpu_count == 1 && s.gpu_milli < kMilli) d->tag = 0;
-  else if (s.gpu_milli == kMilli) d->tag = (int8_t)s.gpu_count;
-  else d->tag = -2;
-  d->tmask = s.type_mask;
-  d->ref = s.ref;
-  d->flags = s.is_delete ? kPodDelete : 0u;
-  return KSIM_OK;
-}
 
 int ksim_engine_set_nodes(ksim_engine* e, int replica, const ksim_node* nodes) {
   if (!e || !nodes || replica < 0 || replica >= e->R) return KSIM_EINVAL;
@@ -3432,38 +3100,7 @@ int ksim_engine_load_events(ksim_engine* e, int replica, const ksim_pod* events,
     }
   }
   // pod classes for k_memo: the distinct Filter + Score requests of the creation events
-  {
-    std::vector<PodDev>& cls = e->h_cls[replica];
-    std::vector<int>& cn = e->h_cls_n[replica];
-    cls.clear();
-    cn.clear();
-    std::vector<std::pair<std::vector<int32_t>, int>> seen;  // small: linear probe by sorted insert
-    auto key_of = [](const PodDev& q) {
-      return std::vector<int32_t>{q.cpu_req, q.cpu_nz, q.mem, q.milli, q.num, (int32_t)q.tmask};
-    };
-    for (int i = 0; i < n; ++i) {
-      if (h[i].flags & kPodDelete) { h[i].pad = -1; continue; }
-      const std::vector<int32_t> k = key_of(h[i]);
-      auto it = std::lower_bound(seen.begin(), seen.end(), k,
-                                 [](const std::pair<std::vector<int32_t>, int>& a, const std::vector<int32_t>& b) {
-                                   return a.first < b;
-                                 });
-      int id;
-      if (it != seen.end() && it->first == k) {
-        id = it->second;
-      } else {
-        id = (int)cls.size();
-        seen.insert(it, {k, id});
-        cls.push_back(h[i]);
-        cls.back().pad = id;
-        cn.push_back(0);
-      }
-      h[i].pad = id;
-      ++cn[id];
-    }
-    e->h_ev_cls[replica].resize(n);
-    for (int i = 0; i < n; ++i) e->h_ev_cls[replica][i] = h[i].pad;
-  }
+  classify_events(h, e->h_cls[replica], e->h_cls_n[replica], e->h_ev_cls[replica]);
   KSIM_HIP(hipSetDevice(e->device));
   // the replica's buffers afresh: a failed alloc leaves its buffer empty, so the replica points at live memory or at
   // none, and has no events until both buffers are there
@@ -3821,10 +3458,10 @@ static void plan_order(const ksim_engine* e, RunPlan& pl) {
     if (count) pl.groups.push_back(g);
   };
   if (e->split_fgd) {  // the wide FGD replicas (k_memo) first, then the one-workgroup ones (k_hmemo): the plans' orders
-    pl.order = e->mplan_reps;
-    pl.order.insert(pl.order.end(), e->hplan_reps.begin(), e->hplan_reps.end());
-    add(POL_FGD, (int)e->mplan_reps.size());
-    add(kPolFgdH, (int)e->hplan_reps.size());
+    pl.order = e->memo.reps;
+    pl.order.insert(pl.order.end(), e->hmemo.reps.begin(), e->hmemo.reps.end());
+    add(POL_FGD, (int)e->memo.reps.size());
+    add(kPolFgdH, (int)e->hmemo.reps.size());
   }
   for (int pol = e->split_fgd ? POL_BESTFIT : POL_FGD; pol <= POL_PWR_FGD; ++pol) {
     int c = 0;
@@ -3849,12 +3486,12 @@ static void plan_kernels(const ksim_engine* e, const RunEnv& env, RunPlan& pl) {
     const bool fgd = g.kind == POL_FGD && e->run_mode != 2;
     if (g.kind == kPolRandomGo) {  // one workgroup per replica
       g.kernel = kRunRandomGo;
-    } else if (fgd && e->mplan_ok) {  // (a split FGD run's wide group is launched first, behind its gate)
+    } else if (fgd && e->memo.ok) {  // (a split FGD run's wide group is launched first, behind its gate)
       g.kernel = kRunMemo;
       pl.concurrent = pl.concurrent && e->split_fgd;
-    } else if ((fgd || g.kind == kPolFgdH) && e->hplan_ok) {  // concurrent at one workgroup per replica
+    } else if ((fgd || g.kind == kPolFgdH) && e->hmemo.ok) {  // concurrent at one workgroup per replica
       g.kernel = kRunHmemo;
-      pl.concurrent = pl.concurrent && (g.kind == kPolFgdH || e->hplan->K == 1);
+      pl.concurrent = pl.concurrent && (g.kind == kPolFgdH || e->hmemo.plan.K == 1);
     } else {
       const int K0 = replay_fit(e, pl.general, g);
       if (g.kind != kPolFgdH) pl.concurrent = pl.concurrent && g.K == 1;
@@ -3939,7 +3576,7 @@ static RunPlan make_run_plan(const ksim_engine* e, const RunEnv& env) {
     g.side = !pl.concurrent || j < 0 ? -1 : (j == 0 || nq == 1) ? 0 : 1 + (j - 1) % (nq - 1);
     if (g.kind == kPolFgdH) pl.fgd_cus += g.count;
     else if (g.kind == POL_FGD && e->run_mode != 2)
-      pl.fgd_cus += e->mplan_ok ? e->mplan->nwg : g.count * (e->hplan_ok ? e->hplan->K : 1);
+      pl.fgd_cus += e->memo.ok ? e->memo.plan.nwg : g.count * (e->hmemo.ok ? e->hmemo.plan.K : 1);
   }
   return pl;
 }
@@ -4072,7 +3709,7 @@ static int launch_gated(ksim_engine* e, bool gate, int n, const char* what,
 // workgroups could hold the CUs a wide replica's exchange waits on.
 static int launch_memo_group(ksim_engine* e, const RunEnv& env, const RunPlan& plan, int gi, hipStream_t gs, int max_ev) {
   const PlanGroup& g = plan.groups[gi];
-  const MemoPlan& pl = *e->mplan;
+  const MemoPlan& pl = e->memo.plan;
   const bool gate = plan.concurrent && gi + 1 < (int)plan.groups.size();
   const int rc = launch_gated(e, gate, pl.nwg, "FGD k_memo", [&](int* flags, int epoch, bool*) {
     return launch_memo(e, env, pl, g.count, g.first, max_ev, gs, flags, epoch);
@@ -4090,7 +3727,7 @@ static int launch_memo_group(ksim_engine* e, const RunEnv& env, const RunPlan& p
 // in 2 s lets the launches go on, it orders work, it decides nothing).
 static int launch_hmemo_group(ksim_engine* e, const RunEnv& env, const RunPlan& plan, int gi, hipStream_t gs, int max_ev) {
   const PlanGroup& g = plan.groups[gi];
-  const int K = e->hplan->K;
+  const int K = e->hmemo.plan.K;
   const bool gate = plan.concurrent && gi + 1 < (int)plan.groups.size() && K == 1 && env.gate;
   const int rc = launch_gated(e, gate, g.count, "FGD k_hmemo", [&](int* flags, int epoch, bool* gated) {
     return launch_hmemo(e, env, g.count, g.first, max_ev, gs, flags, epoch, gated);
@@ -4317,7 +3954,7 @@ int ksim_engine_run(ksim_engine* e) {
   e->last_gate = 0;
   e->last_ovl = 0;
   e->last_kernels.clear();
-  int rc = prepare_memo(e, max_ev);
+  int rc = prepare_memo(e, env, max_ev);
   if (rc) return rc;
   KSIM_HIP(hipEventRecord(e->ev0, e->stream));
   rc = reset_state(e);
@@ -4550,21 +4187,17 @@ static int run_hmemo_peer(ksim_engine* e, const RunEnv& env, int max_ev) {
     return KSIM_ENOTSUP;
   const int world = e->shard_world;
   const int nmax = (e->n_global + world - 1) / world;
-  int K = std::max(1, 64 / world);
-  int S = std::max(kFan, (nmax + K - 1) / K + kFan - 1) / kFan * kFan;
-  if (S > kMaxNb * kFan) {
-    S = kMaxNb * kFan;
-    K = (nmax + S - 1) / S;
-  }
+  const HSlices sl = hmemo_slices(nmax, std::max(1, 64 / world), kClampKeepK);
+  const int K = sl.K, S = sl.S;
   const int Kt = world * K;
   if (Kt > 256 || e->N > K * S) return KSIM_ENOTSUP;
   const int stride = std::max(max_ev, 1);
   hipStream_t st = e->stream;
   const int zero = 0;
   KSIM_HIP(hipMemcpyAsync(e->d_replist.p, &zero, sizeof(int), hipMemcpyHostToDevice, st));
-  int rc = prepare_hmemo(e, std::vector<int>{0}, max_ev, K, S);
+  int rc = prepare_hmemo(e, env, std::vector<int>{0}, max_ev, K, S);
   if (rc) return rc;
-  if (!e->hplan_ok) return KSIM_ENOTSUP;
+  if (!e->hmemo.ok) return KSIM_ENOTSUP;
   e->mplan_dirty = true;
   KSIM_HIP(hipMemcpyAsync(e->d_nodes.p, e->d_nodes_init.p, sizeof(NodeRec) * (size_t)e->N, hipMemcpyDeviceToDevice, st));
   KSIM_HIP(hipMemcpyAsync(e->d_tags.p, e->d_tags_init.p, sizeof(uint16_t) * e->tags_stride, hipMemcpyDeviceToDevice, st));
@@ -4581,20 +4214,18 @@ static int run_hmemo_peer(ksim_engine* e, const RunEnv& env, int max_ev) {
   a.epoch = e->peer_epoch;
   for (int q = 0; q < world; ++q) a.peer[q] = e->peers[q];
   if (e->has_delete[0]) {
-    if ((rc = e->d_h_hist.ensure((size_t)K * stride))) return rc;
-    a.hist = e->d_h_hist.p;
+    if ((rc = e->hmemo.hist.ensure((size_t)K * stride))) return rc;
+    a.hist = e->hmemo.hist.p;
   }
   KSIM_HIP(hipMemsetAsync(e->d_fail.p, 0, sizeof(int), st));
-  const bool gen = a.delay != 0;
-  const void* f = Kt <= 64 ? (gen ? (const void*)k_hmemo<1, true> : (const void*)k_hmemo<1, false>)
-                           : (gen ? (const void*)k_hmemo<4, true> : (const void*)k_hmemo<4, false>);
-  if (K > resident_cap(e, f, e->hplan->lds)) return KSIM_ERANGE;
+  const void* f = hmemo_kernel(hmemo_form(kHPeer, Kt, false, a.delay, false));
+  if (K > resident_cap(e, f, e->hmemo.plan.lds)) return KSIM_ERANGE;
   KSIM_HIP(hipEventRecord(e->ev0, st));
   const TypDev* tpp = e->d_tp.p;
   // a plain launch: K <= 64 one-per-CU workgroups are resident (checked above), and a cooperative launch
   // takes the device's one global-wave-sync resource, which a second shard process on the same device
   // would wait for behind the first's persistent kernel
-  if ((rc = launch_persistent(f, K, kHBlock, e->hplan->lds, st, false, a, tpp))) return rc;
+  if ((rc = launch_persistent(f, K, kHBlock, e->hmemo.plan.lds, st, false, a, tpp))) return rc;
   KSIM_HIP(hipEventRecord(e->ev1, st));
   KSIM_HIP(hipStreamSynchronize(st));
   int fail = 0;
@@ -4614,8 +4245,8 @@ static int run_hmemo_peer(ksim_engine* e, const RunEnv& env, int max_ev) {
 // shards' slices (K per shard, S ranks each), and each pod step's slice maxima go through ONE exchange of
 // world x K granule columns: selectHost over the union (generic_scheduler.go:187-212), the owner of the
 // winner binds.  Results carry global ranks as the k_step shards' do (ksim/shard.py merge_results).
-static bool hmemo_group_eligible(ksim_engine* const* engines, int world) {
-  if (variant("shard_hmemo", 1) == 0) return false;
+static bool hmemo_group_eligible(ksim_engine* const* engines, int world, const RunEnv& env) {
+  if (!env.shard_hmemo) return false;
   if (!score_table()) return false;
   for (int k = 0; k < world; ++k) {
     const ksim_engine* e = engines[k];
@@ -4730,10 +4361,8 @@ static int run_hmemo_group(ksim_engine* const* engines, int world, const RunEnv&
   const int stride = std::max(max_ev, 1);
   int nmax = 1;
   for (int k = 0; k < world; ++k) nmax = std::max(nmax, engines[k]->N);
-  const int want = std::max(1, std::min(64, e0->cus / world));
-  int S = std::max(kFan, (nmax + want - 1) / want + kFan - 1) / kFan * kFan;
-  S = std::min(S, kMaxNb * kFan);
-  const int K = (nmax + S - 1) / S;
+  const HSlices sl = hmemo_slices(nmax, std::max(1, std::min(64, e0->cus / world)), kClamp);
+  const int K = sl.K, S = sl.S;
   const int Kt = world * K;
   if (K < 1 || Kt > 256 || K * S < nmax) return KSIM_OK;
   std::vector<HMemoArgs> args(world);
@@ -4742,15 +4371,13 @@ static int run_hmemo_group(ksim_engine* const* engines, int world, const RunEnv&
     ksim_engine* e = engines[k];
     const int zero = 0;
     KSIM_HIP(hipMemcpyAsync(e->d_replist.p, &zero, sizeof(int), hipMemcpyHostToDevice, e->stream));
-    int rc = prepare_hmemo(e, std::vector<int>{0}, max_ev, K, S);
+    int rc = prepare_hmemo(e, env, std::vector<int>{0}, max_ev, K, S);
     if (rc) return rc;
-    if (!e->hplan_ok) return KSIM_OK;
+    if (!e->hmemo.ok) return KSIM_OK;
     e->mplan_dirty = true;  // the unsharded plan is not this one
-    lds = std::max(lds, e->hplan->lds);
+    lds = std::max(lds, e->hmemo.plan.lds);
   }
-  const bool gen = env.hdelay != 0;  // the hdelay test knob: the general instantiation
-  const void* f = Kt <= 64 ? (gen ? (const void*)k_hmemo_group<1, true> : (const void*)k_hmemo_group<1, false>)
-                           : (gen ? (const void*)k_hmemo_group<4, true> : (const void*)k_hmemo_group<4, false>);
+  const void* f = hmemo_kernel(hmemo_form(kHGroup, Kt, false, env.hdelay, false));
   if (Kt > resident_cap(e0, f, lds)) return KSIM_OK;
   hipStream_t st = e0->stream;
   KSIM_HIP(hipSetDevice(e0->device));
@@ -4772,9 +4399,9 @@ static int run_hmemo_group(ksim_engine* const* engines, int world, const RunEnv&
     a.gran = e0->d_ggran.p;
     a.fail = e0->d_fail.p;
     if (e->has_delete[0]) {
-      rc = e->d_h_hist.ensure((size_t)K * stride);
+      rc = e->hmemo.hist.ensure((size_t)K * stride);
       if (rc) return rc;
-      a.hist = e->d_h_hist.p;
+      a.hist = e->hmemo.hist.p;
     }
     args[k] = a;
   }
@@ -4825,7 +4452,7 @@ int ksim_shard_group_run(ksim_engine* const* engines, int world) {
   }
   KSIM_HIP(hipSetDevice(e0->device));
   const RunEnv env = read_env();
-  if (hmemo_group_eligible(engines, world)) {
+  if (hmemo_group_eligible(engines, world, env)) {
     bool done = false;
     const int rc = run_hmemo_group(engines, world, env, max_ev, &done);
     if (!rc && done)

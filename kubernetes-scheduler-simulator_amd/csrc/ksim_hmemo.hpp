@@ -42,14 +42,10 @@
 namespace ksim_hmemo {
 
 using namespace ksim;
+using namespace ksim_plan::hmemo;  // kFan, kMaxNb, kMaxClasses, kMaxGroups, kMaxItems, kHRankMax, kMtPresent, hmemo_layout
 
 constexpr int kHBlock = 1024;
 constexpr int kHWaves = kHBlock / 64;
-constexpr int kFan = 64;              // keys per L1 block (one wave / one quarter-wave dwordx4 row)
-constexpr int kMaxNb = 64;            // L1 blocks per class (N <= 4096)
-constexpr int kMaxClasses = 1024;     // one class-pass thread each
-constexpr int kMaxGroups = 128;
-constexpr int kMaxItems = 1 + 8 * kMaxGroups;
 constexpr int kEvBuf = 128;
 constexpr int kQuarters = kHBlock / 16;
 constexpr int kMaxPeers = 16;  // shard processes of a device exchange (ksim_engine_set_shard: world <= 16)
@@ -60,7 +56,6 @@ constexpr int kCW = kHWaves - 1 - kFW; // class waves (kFW+1..15)
 // (15 - g for a share pod placed on GPU g, 0 otherwise).  0 = infeasible.  Max key = max score,
 // ties to the smallest name (selectHost, generic_scheduler.go:187-212); over one node's candidates
 // the max keeps the lowest GPU index reaching the max (fgd_score.go:128).  Non-negative as int32.
-constexpr int kHRankMax = (1 << 20) - 1;
 KSIM_HD unsigned hkey(int score, int rank, int gf) {
   return ((unsigned)(score + 1) << 24) | ((unsigned)(kHRankMax - rank) << 4) | (unsigned)gf;
 }
@@ -129,7 +124,6 @@ struct HMemoArgs {
   const double* na;
   int Mtab, Mslots;
 };
-constexpr uint32_t kMtPresent = 1u << 31;
 constexpr int kNaStride = 8008;  // totals 0 .. 8 x 1000 (kMaxGpu x kMilli), padded
 constexpr int kHProf = 16;  // 0-6 phase sums, 7 items, 8 flagged classes, 9 refresh steps, 10 clock, 11 wall
 
@@ -159,38 +153,7 @@ struct __align__(16) HShared {
   unsigned dead[32];   // class slots with no feasible node (create-only streams: for good)
 };
 static_assert(sizeof(HShared) % 16 == 0, "keep the dynamic regions 16-B aligned");
-
-// Dynamic LDS after HShared (16-B aligned regions).
-struct HLayout {
-  size_t cls, gpod, F, l1, l2, nodes, last, cnt, bx, bx2, cgrp, flist, code, igrp, fnew, fold, gbase, gkey, ctp, mto, total;
-};
-KSIM_HD size_t halign(size_t x) { return (x + 15) & ~(size_t)15; }
-KSIM_HD HLayout hmemo_layout(int N, int Cmax, int Gmax, int nb, bool l2, int Mtab) {
-  HLayout L;
-  size_t o = sizeof(HShared);
-  L.cls = o;   o = halign(o + (size_t)Cmax * sizeof(PodDev));
-  L.gpod = o;  o = halign(o + (size_t)Gmax * sizeof(PodDev));
-  L.F = o;     o = halign(o + (size_t)kMaxItems * sizeof(double));
-  L.l1 = o;    o = halign(o + (size_t)Cmax * nb * 4);
-  L.l2 = o;    o = halign(o + (l2 ? (size_t)Cmax * nb * 4 : 0));
-  L.nodes = o; o = halign(o + (size_t)N * sizeof(NodeRec));
-  L.last = o;  o = halign(o + (size_t)N * 4);
-  L.cnt = o;   o = halign(o + (size_t)Cmax * 4);
-  L.bx = o;    o = halign(o + (size_t)Cmax * 4);
-  L.bx2 = o;   o = halign(o + (l2 ? (size_t)Cmax * 4 : 0));
-  L.cgrp = o;  o = halign(o + (size_t)Cmax * 2);
-  L.flist = o; o = halign(o + (size_t)Cmax * 2);
-  L.code = o;  o = halign(o + (size_t)2 * kMaxItems);  // the F list, double-buffered like d's records
-  L.igrp = o;  o = halign(o + (size_t)2 * kMaxItems);
-  L.fnew = o;  o = halign(o + (size_t)Cmax);
-  L.fold = o;  o = halign(o + (size_t)Cmax);
-  L.gbase = o; o = halign(o + (size_t)Gmax * 2 * 2);
-  L.gkey = o;  o = halign(o + (size_t)Gmax * 2 * 4);  // every score group's key on d, double-buffered like the list
-  L.ctp = o;   o = halign(o + (size_t)Mtab * sizeof(TypDev));  // the per-model tables (typed replicas)
-  L.mto = o;   o = halign(o + (Mtab > 0 ? (size_t)KSIM_MAX_TYPES * 4 : 0));
-  L.total = o;
-  return L;
-}
+static_assert(sizeof(HShared) == kSharedBytes, "hmemo_layout (ksim_plan.hpp) starts the dynamic regions after HShared");
 
 // Global-address-space access (flat loads / stores also count in lgkmcnt, so every later LDS wait
 // would stall on them; global_* ones count in vmcnt only).

@@ -15,7 +15,7 @@
 // A device buffer: the pointer and its capacity in one owning, movable object.
 template <typename T>
 struct DevBuf {
-  T* p = nullptr;   // kernels take it by name: args.keys = e->d_h_keys.p
+  T* p = nullptr;   // kernels take it by name: args.keys = e->hmemo.keys.p
   size_t cap = 0;   // elements asked for by the alloc() / ensure() that allocated p
 
   DevBuf() = default;
@@ -157,6 +157,16 @@ struct RunEnv {
   bool group_times = false;  // KSIM_GROUP_TIMES=1
   int side_streams = 4;      // of a concurrent run: GPU_MAX_HW_QUEUES, KSIM_SIDE_STREAMS over it, 1..kSideStreams
   bool skip = true, gate = true, scan1_mix = true, report_overlap = true, pf_memo = true;  // KSIM_VARIANT
+  // KSIM_VARIANT, the memoised FGD replays (ksim_plan.hpp; the first three take effect when a plan is made)
+  bool memo_decider = false;  // run_mode 0 plans k_memo's decider form
+  bool hl2 = false;           // k_hmemo at one workgroup per replica keeps the second maxima beside L1
+  bool hmodel = true;         // k_hmemo's per-model tables of typed replicas (0: the whole table for every model)
+  int hpf = 1;                // k_hmemo, one workgroup per replica: 1 = wave 0 lists the next refresh (the default since r04:
+                              // C4 190.7 -> 178-185 ms, C2 run_mode 5 50.3 -> 47.7 ms, profiles/r04/memo/ab_runs.txt),
+                              // 2 = touches its flagged rows, 0 = off (4: the wide form lists on wave 0 too)
+  int hprune = 64;            // k_hmemo (A/B): the F list's group pruning for replicas with more than this many typical
+                              // pods (-1: every replica; default 64: the large typed tables, where the F rounds bound the step)
+  bool shard_hmemo = true;    // an in-process shard group of FGD replicas on k_hmemo_group (0: the per-pod k_step path)
   bool force_report_overlap = false;                                                       // KSIM_TEST report_overlap
   long pf_memo_ver0 = 0;                                                                   // KSIM_TEST
   bool pf_guess = true;
@@ -178,6 +188,12 @@ static RunEnv read_env() {
   v.scan1_mix = variant("scan1_mix", 1) != 0;
   v.report_overlap = variant("report_overlap", 1) != 0;
   v.pf_memo = variant("pf_memo", 1) != 0;
+  v.memo_decider = variant("memo_decider", 0) == 1;
+  v.hl2 = variant("hl2", 0) == 1;
+  v.hmodel = variant("hmodel", 1) != 0;
+  v.hpf = (int)variant("hpf", 1) & 7;
+  v.hprune = (int)variant("hprune", 64);
+  v.shard_hmemo = variant("shard_hmemo", 1) != 0;
   v.force_report_overlap = test_knob("report_overlap", 0) != 0;
   v.pf_memo_ver0 = test_knob("pf_memo_ver0", 0);
   v.pf_guess = test_knob("pf_guess", 1) != 0;

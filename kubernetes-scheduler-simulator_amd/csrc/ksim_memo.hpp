@@ -35,12 +35,11 @@
 namespace ksim_memo {
 
 using namespace ksim;
+using namespace ksim_plan::memo;  // kMaxCw, the fold buffers' shape, kMemoMaxRank, memo_layout
 
 constexpr int kMBlock = 1024;
 constexpr int kMWaves = kMBlock / 64;
-constexpr int kMaxCw = 64;                 // class slots per workgroup (one wave-0 lane each)
 constexpr int kMaxItems = 1 + 8 * kMaxCw;  // F evaluations per refresh: current + 8 per request
-constexpr int kFoldRows = 6;               // Q1, Q2 (+Q3 frag), Q4, XL, XR, NA
 constexpr int kCritWaves = 9;              // owner: waves 1..9 evaluate the step's class on d
 // waves that scan the next create event's class for its top-2 during phase A (bit w = wave w): outside wave 0,
 // the owner's critical waves and the list wave, the same on every workgroup
@@ -48,11 +47,6 @@ constexpr unsigned kScanMask = 0x7C00u;    // waves 10-14
 constexpr int kScanWaves = __builtin_popcount(kScanMask);
 static_assert((kScanMask & ((2u << kCritWaves) - 1u)) == 0u && (kScanMask >> (kMWaves - 1)) == 0u,
               "the scan waves are idle in phase A on an owner too");
-// fold-buffer rows 66 doubles apart: lanes 0-5 fold rows 0-5 with ds_read_b128, whose bank is
-// (a/4) % 64; a 64-double (2 x 256 B) stride put all six rows on the same banks (6-way conflict),
-// 66 puts row b on banks 4b..4b+3
-constexpr int kFoldStride = 66;
-constexpr int kFoldBuf = kFoldRows * kFoldStride;  // doubles per evaluating wave
 constexpr int kEvBuf = 128;
 constexpr unsigned kSpinLimit = 1u << 22;
 constexpr int kMaxDeadWords = 32;  // dead-class bitmask: class ids < 1024
@@ -136,12 +130,12 @@ struct __align__(16) MemoShared {
   unsigned long long prof[kProfPhases];
 };
 static_assert(sizeof(MemoShared) % 16 == 0, "keep the node records 16-B aligned");
+static_assert(sizeof(MemoShared) == kSharedBytes, "memo_layout (ksim_plan.hpp) starts the node records after MemoShared");
 
 // Packed 32-bit key of (pod class, node): [30:24] score + 1 | [23:12] 4095 - rank | [11:8] gpu
 // field (15 - g for a share pod placed on GPU g, 0 otherwise) | 0.  0 = infeasible.  Max key =
 // max score, ties to the smallest name (selectHost, generic_scheduler.go:187-212); for one node
 // the max over its candidates keeps the lowest GPU index (fgd_score.go:128).
-constexpr int kMemoMaxRank = 0xFFF;
 KSIM_HD unsigned pack_key32(int score, int rank, int gf) {
   return ((unsigned)(score + 1) << 24) | ((unsigned)(kMemoMaxRank - rank) << 12) | ((unsigned)gf << 8);
 }
@@ -408,6 +402,7 @@ struct __align__(16) DeciderScratch {
   int finished;
   uint8_t item_x[kDItems + 5], item_code[kDItems + 5];
 };
+static_assert(sizeof(DeciderScratch) == kDeciderBytes, "memo_layout (ksim_plan.hpp) keeps room for the decider's scratch");
 
 __device__ __forceinline__ int lds_load(const int* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -785,6 +780,9 @@ __global__ __launch_bounds__(kMBlock) void k_memo(MemoArgs a, const TypDev* __re
   const TypDev* __restrict__ tp = tp_all + (size_t)r * kMaxTypical;
   const int N = a.N, Cw = a.Cw;
   const int* rank2idx = reinterpret_cast<const int*>(rp.tags + (size_t)N * kTagStride);
+  // the carving memo_layout (ksim_plan.hpp) describes: nodes, keys, fold, last.  Written out here, since taking the
+  // offsets from memo_layout moved registers and scratch in the step loop; the static_asserts on the two structs'
+  // sizes and tests/native_host/plan_check.cpp (the layout's regions against these expressions) tie the two.
   NodeRec* s_nodes = reinterpret_cast<NodeRec*>(smem + sizeof(MemoShared));
   unsigned* s_keys = kHKeys ? a.hkeys + (size_t)blockIdx.x * Cw * N : reinterpret_cast<unsigned*>(s_nodes + N);
   double* s_fold = reinterpret_cast<double*>(
@@ -1391,13 +1389,6 @@ __global__ void k_memo_finish(ReplicaDev* reps, const int* rep_list, int N) {
   const size_t h = (size_t)idx * kTagStride + tag;
   unsigned* word = reinterpret_cast<unsigned*>(rp.tags) + (h >> 1);
   atomicAdd(word, (unsigned)(del ? -1 : 1) << (16 * (h & 1)));
-}
-
-// LDS bytes of k_memo's dynamic region (must match the carving in the kernel).
-inline size_t memo_lds(int N, int Cw, int nfw, bool hkeys = false) {
-  const size_t keys = hkeys ? 0 : (std::max((size_t)Cw * N * 4, sizeof(DeciderScratch)) + 15) & ~(size_t)15;
-  const size_t fold = std::max((size_t)nfw * kFoldBuf * 8, ((size_t)N * 8 + 15) & ~(size_t)15);
-  return sizeof(MemoShared) + (size_t)N * sizeof(NodeRec) + keys + fold + (size_t)N * 4;
 }
 
 }  // namespace ksim_memo
