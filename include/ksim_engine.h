@@ -420,6 +420,31 @@ int  ksim_engine_deschedule(ksim_engine* e, int policy, double ratio);
 int  ksim_engine_get_victims(ksim_engine* e, int replica, ksim_victim* out, int cap, int* n_out, int* budget_out);
 int  ksim_engine_last_deschedule_ms(ksim_engine* e, double* ms);
 
+/* The cosSim policy (deschedule.go:49-92 descheduleClusterOnCosSim; the victim of one node: findVictimPodOnCosSim,
+ * deschedule_utils.go:15-45; the node order: sortNodeStatusByResource, :47-71), planned on the device from the
+ * same inputs with the same bound pods and budget.  A node is a candidate when its CPU left is below
+ * cpu_bar_milli and one of its own GPUs has more than gpu_bar_milli left (the reference hard-codes 2000 and
+ * 500).  The candidates are walked by total milli-GPU left, descending, then name_rank; on each, the pod with
+ * the least cosine similarity between [CPU left, total milli-GPU left] of the node after NodeResource.Add and
+ * the pod's [MilliCpu, MilliGpu x GpuNumber] is the victim: 0 <= similarity < 1 only, the lowest creation-event
+ * index among equals, one victim a node, until the budget is used.  A node without a victim uses no budget.
+ *   KSIM_EINVAL   ratio < 0 or NaN, a negative bar       KSIM_ENOTSUP  node-sharded engine
+ *   KSIM_ESTATE   no completed run                        KSIM_ENODEV   no gfx950 device
+ * An engine holds one plan: after ksim_engine_deschedule_cossim, ksim_engine_get_victims returns KSIM_ESTATE,
+ * and ksim_engine_get_cos_victims does after ksim_engine_deschedule.  ksim_engine_get_cos_victims follows
+ * ksim_engine_get_victims; ksim_engine_last_deschedule_ms reports the last plan of either kind. */
+typedef struct {
+    int32_t event;            /* creation event index of the victim */
+    int32_t node;             /* node it is evicted from */
+    int32_t gpu_mask;         /* devices it held */
+    int32_t reserved;
+    int64_t gpu_left_milli;   /* the node's total milli-GPU left at plan time (its sort key) */
+    double  similarity;       /* what elected the pod, in [0, 1) */
+} ksim_cos_victim;            /* 32 bytes */
+int  ksim_engine_deschedule_cossim(ksim_engine* e, double ratio, int64_t cpu_bar_milli, int64_t gpu_bar_milli);
+int  ksim_engine_get_cos_victims(ksim_engine* e, int replica, ksim_cos_victim* out, int cap, int* n_out,
+                                 int* budget_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,8 @@
 //                     (NodeResource.Add, pkg/type/resource.go:482-512), and the bound-pod count;
 //   k_desched_select  one workgroup per replica: the pop / pick / re-key loop of the policy over those
 //                     values, victims in eviction order.
+// The cosSim policy (:49-92; the victim of one node: findVictimPodOnCosSim, deschedule_utils.go:15-45) shares
+// k_desched_mark and has k_cos_eval and k_cos_select of its own, at the end of this file.
 // The rescheduling itself is the ordinary replay of the extended event stream (ksim/desched.py).
 // No kernel here waits for another workgroup, and nothing is on the per-pod path.
 //
@@ -28,18 +30,14 @@ namespace ksim_ds {
 
 using namespace ksim;
 
-// NodeResource.Add(podRes, gpu ids) (resource.go:482-512) on a node state, then F of the result.
-// CPU left grows by PodResource.MilliCpu (cpu_nz); a pod with GPUs adds its per-GPU milli to every
-// device named in `mask`.  False (the reference skips the pod) when the CPU left would exceed the
-// capacity, a named device does not exist or a device would exceed 1000 milli left.  *f_after is
-// written only on success.  frag_F is used unchanged: same per-bin order, no fused multiply-add.
-template <bool kTyped>
-KSIM_HD bool victim_eval(int cpuL, const int (&gl)[kMaxGpu], int gpu_cnt, uint32_t typebit, int cap, int cpu_nz,
-                         int milli, int num, unsigned mask, const TypDev* __restrict__ tp, int ncpu, int nt,
-                         double* f_after) {
+// NodeResource.Add(podRes, gpu ids) (resource.go:482-512) on a node state: the verdict, and on success the
+// state after it.  CPU left grows by PodResource.MilliCpu (cpu_nz); a pod with GPUs adds its per-GPU milli to
+// every device named in `mask`.  False (the reference skips the pod) when the CPU left would exceed the
+// capacity, a named device does not exist or a device would exceed 1000 milli left.
+KSIM_HD bool node_add(int cpuL, const int (&gl)[kMaxGpu], int gpu_cnt, int cap, int cpu_nz, int milli, int num,
+                      unsigned mask, long long* cpu_after, int (&g2)[kMaxGpu]) {
   const long long cpu_new = (long long)cpuL + cpu_nz;
   if (cpu_new > (long long)cap) return false;
-  int g2[kMaxGpu];
   bool ok = true;
 #pragma unroll
   for (int g = 0; g < kMaxGpu; ++g) {
@@ -49,9 +47,54 @@ KSIM_HD bool victim_eval(int cpuL, const int (&gl)[kMaxGpu], int gpu_cnt, uint32
     g2[g] = v;
   }
   if (num > 0 && (mask >> kMaxGpu) != 0u) ok = false;
-  if (!ok) return false;
+  *cpu_after = cpu_new;
+  return ok;
+}
+
+// Add, then F of the result.  *f_after is written only on success.  frag_F is used unchanged: same per-bin
+// order, no fused multiply-add.
+template <bool kTyped>
+KSIM_HD bool victim_eval(int cpuL, const int (&gl)[kMaxGpu], int gpu_cnt, uint32_t typebit, int cap, int cpu_nz,
+                         int milli, int num, unsigned mask, const TypDev* __restrict__ tp, int ncpu, int nt,
+                         double* f_after) {
+  long long cpu_new;
+  int g2[kMaxGpu];
+  if (!node_add(cpuL, gl, gpu_cnt, cap, cpu_nz, milli, num, mask, &cpu_new, g2)) return false;
   *f_after = frag_F<kTyped>((int)cpu_new, g2, typebit, tp, ncpu, nt);
   return true;
+}
+
+// cosSim (deschedule_utils.go:15-45 findVictimPodOnCosSim): the cosine of [CPU left, total milli-GPU left] of
+// the node after Add and [MilliCpu, MilliGpu x GpuNumber] of the pod, as CalculateVectorCosineSimilarity
+// (pkg/utils/utils.go:1196-1218) writes it: three running sums over the two components, sqrt of the two
+// magnitudes, inner / (m1 * m2).  Every component is an integer far below 2^26, so the sums are exact; only the
+// two roots, their product and the quotient round, each correctly (no fused multiply-add, no fast math).
+// -1 (the reference skips the pod) when Add fails, a magnitude is zero or the value leaves
+// [-1e-3, 1 + 1e-3] (GetResourceSimilarity, utils.go:1181-1193).
+KSIM_HD double cos_similarity(int cpuL, const int (&gl)[kMaxGpu], int gpu_cnt, int cap, int cpu_nz, int milli, int num,
+                              unsigned mask) {
+  long long cpu_new;
+  int g2[kMaxGpu];
+  if (!node_add(cpuL, gl, gpu_cnt, cap, cpu_nz, milli, num, mask, &cpu_new, g2)) return -1.0;
+  int tot = 0;
+#pragma unroll
+  for (int g = 0; g < kMaxGpu; ++g) tot += g2[g];
+  const double n0 = (double)cpu_new, n1 = (double)tot;
+  const double p0 = (double)cpu_nz, p1 = (double)((long long)milli * (long long)num);
+  double m1 = 0.0, m2 = 0.0, inner = 0.0;
+  m1 += n0 * n0;
+  m2 += p0 * p0;
+  inner += n0 * p0;
+  m1 += n1 * n1;
+  m2 += p1 * p1;
+  inner += n1 * p1;
+  m1 = __builtin_sqrt(m1);
+  m2 = __builtin_sqrt(m2);
+  if (m1 == 0.0 || m2 == 0.0) return -1.0;
+  const double s = inner / (m1 * m2);
+  const double delta = 1e-3;
+  if (s < 0.0 - delta || s > 1.0 + delta) return -1.0;
+  return s;
 }
 
 // What k_desched_eval leaves per event (32 B).  node < 0: not a candidate (a delete event, a pod that
@@ -330,6 +373,176 @@ __global__ __launch_bounds__(kSelBlock) void k_desched_select(DsArgs a) {
       nkey[best.idx] = 0ull;
     }
     __syncthreads();  // the re-key and the eviction mark before the next pop; s_pick / s_pod free again
+  }
+  if (tid == 0) a.n_vict[r] = nv;
+}
+
+// ---- cosSim (deschedule.go:49-92 descheduleClusterOnCosSim) ----------------------------------------------------
+// The node state is the plan-time state for every pod and every node, a node gives one victim at most and the
+// walk only counts them, so the plan is: per bound pod its similarity (k_cos_eval), per node the arg-min of
+// (similarity, event) over the pods that can be elected, the nodes that pass both bars and have such a pod in
+// the order of sortNodeStatusByResource, cut at the budget (k_cos_select).
+
+// What k_cos_eval leaves per event (16 B).  node < 0: not a bound pod, or a record that does not validate.
+struct __align__(16) CosRec {
+  double sim;  // cos_similarity: -1 when the reference skips the pod
+  int32_t node;
+  int32_t gpu_mask;
+};
+static_assert(sizeof(CosRec) == 16, "CosRec layout");
+static_assert(sizeof(ksim_cos_victim) == 32, "ksim_cos_victim layout");
+
+// per-node tables of k_cos_select: the least similarity's bits 8, sort key 8, its pod 4, node index 4
+constexpr int kCosNodeBytes = 24;
+KSIM_HD size_t cos_tab_stride(int N) { return ((size_t)N * kCosNodeBytes + 15) & ~(size_t)15; }
+
+struct CosArgs {
+  const ReplicaDev* reps;
+  const long long* eoff;   // [R + 1]
+  CosRec* rec;             // [Σ E]
+  const uint8_t* gone;     // [Σ E] k_desched_mark's
+  ksim_cos_victim* vict;   // [Σ E]
+  int32_t* bound;          // [R]
+  const int32_t* budget;   // [R]
+  int32_t* n_vict;         // [R]
+  uint8_t* tab;            // [R][cos_tab_stride(N)] when the tables do not fit in LDS, else null
+  long long cpu_bar;       // milliCpuBar: a node at or above it is skipped
+  long long gpu_bar;       // milliGpuBar: some device of the node must have more than it left
+  int N;
+};
+
+// A pod is elected only with 0 <= similarity < 1 (deschedule_utils.go:34, victimPodSimilarity starts at 1).
+// Such doubles are non-negative, so their bit patterns order as integers; + 0.0 folds a negative zero.
+KSIM_HD bool cos_elects(double s) { return s >= 0.0 && s < 1.0; }
+KSIM_HD unsigned long long cos_bits(double s) { return __builtin_bit_cast(unsigned long long, s + 0.0); }
+
+// grid (ceil(E_max / kEvalBlock), R): the candidate record of every event and the replica's bound-pod count.
+__global__ __launch_bounds__(kEvalBlock) void k_cos_eval(CosArgs a) {
+  const int r = (int)blockIdx.y;
+  const ReplicaDev rp = a.reps[r];
+  const int e = (int)blockIdx.x * kEvalBlock + (int)threadIdx.x;
+  bool bound = false;
+  if (e < rp.n_events) {
+    CosRec out;
+    out.sim = -1.0;
+    out.node = -1;
+    out.gpu_mask = 0;
+    const PodDev p = rp.ev[e];
+    const ResultDev res = rp.res[e];
+    bound = !(p.flags & kPodDelete) && res.status == ST_OK && !a.gone[a.eoff[r] + e];
+    // the record is validated before it indexes anything: the node, then the mask against its GPUs
+    if (bound && res.node >= 0 && res.node < a.N && res.gpu_mask >= 0) {
+      const NodeV n = load_node(rp.nodes + res.node);
+      const int cnt = n.gpu_cnt();
+      if (cnt <= kMaxGpu && ((unsigned)res.gpu_mask >> cnt) == 0u) {
+        int gl[kMaxGpu];
+        unpack_gl(n, gl);
+        out.node = res.node;
+        out.gpu_mask = res.gpu_mask;
+        out.sim = cos_similarity(n.cpu_left, gl, cnt, rp.cap[res.node], p.cpu_nz, p.milli, p.num,
+                                 (unsigned)res.gpu_mask);
+      }
+    }
+    a.rec[a.eoff[r] + e] = out;
+  }
+  const unsigned long long m = __ballot(bound);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(a.bound + r, (int)__popcll(m));
+}
+
+// One workgroup per replica.  The arg-min in two passes over the events (the 64-bit similarity and the event do
+// not fit one atomic): the least bits per node, then the least event among the pods that have them.  The nodes
+// that pass both bars and have a victim are compacted (in any order: the sort decides) with the key
+// (8000 - total milli-GPU left) << 32 | name_rank, sorted ascending by a bitonic network over exactly M entries
+// (every exchange moves the smaller key down, so the entries a power of two would add above M, all +inf, never
+// move and are never stored), and the first min(M, budget) are written out.  Ties of the key (name ranks that
+// are not unique) fall back on the node index, so the plan is the same on every run.
+__global__ __launch_bounds__(kSelBlock) void k_cos_select(CosArgs a) {
+  extern __shared__ __align__(16) uint8_t s_dyn[];
+  __shared__ int s_m;
+  const int r = (int)blockIdx.x, tid = (int)threadIdx.x;
+  const ReplicaDev rp = a.reps[r];
+  const int N = a.N, E = rp.n_events;
+  const CosRec* rec = a.rec + a.eoff[r];
+  ksim_cos_victim* vict = a.vict + a.eoff[r];
+  uint8_t* base = a.tab ? a.tab + (size_t)r * cos_tab_stride(N) : s_dyn;
+  unsigned long long* nbits = reinterpret_cast<unsigned long long*>(base);
+  unsigned long long* skey = reinterpret_cast<unsigned long long*>(base + (size_t)N * 8);
+  unsigned* nev = reinterpret_cast<unsigned*>(base + (size_t)N * 16);
+  int* sidx = reinterpret_cast<int*>(base + (size_t)N * 20);
+  constexpr unsigned kNone = 0xFFFFFFFFu;
+
+  if (tid == 0) s_m = 0;
+  for (int i = tid; i < N; i += kSelBlock) {
+    nbits[i] = ~0ull;
+    nev[i] = kNone;
+  }
+  __syncthreads();
+  for (int e = tid; e < E; e += kSelBlock) {
+    const CosRec c = rec[e];
+    if (c.node >= 0 && c.node < N && cos_elects(c.sim)) atomicMin(&nbits[c.node], cos_bits(c.sim));
+  }
+  __syncthreads();
+  for (int e = tid; e < E; e += kSelBlock) {
+    const CosRec c = rec[e];
+    if (c.node >= 0 && c.node < N && cos_elects(c.sim) && cos_bits(c.sim) == nbits[c.node])
+      atomicMin(&nev[c.node], (unsigned)e);
+  }
+  __syncthreads();
+  for (int i = tid; i < N; i += kSelBlock) {
+    if (nev[i] == kNone) continue;
+    const NodeV n = load_node(rp.nodes + i);
+    if ((long long)n.cpu_left >= a.cpu_bar) continue;
+    const int cnt = min(n.gpu_cnt(), kMaxGpu);
+    int gl[kMaxGpu];
+    unpack_gl(n, gl);
+    bool pass = false;
+    int tot = 0;
+#pragma unroll
+    for (int g = 0; g < kMaxGpu; ++g) {
+      pass = pass || (g < cnt && (long long)gl[g] > a.gpu_bar);
+      tot += gl[g];
+    }
+    if (!pass) continue;
+    const int slot = atomicAdd(&s_m, 1);  // < N: one slot per node at most
+    skey[slot] = ((unsigned long long)(unsigned)(kMaxGpu * kMilli - min(tot, kMaxGpu * kMilli)) << 32) |
+                 (unsigned long long)n.name_rank;
+    sidx[slot] = i;
+  }
+  __syncthreads();
+  const int M = s_m;
+  for (unsigned long long k = 2; (k >> 1) < (unsigned long long)M; k <<= 1) {
+    for (unsigned long long j = k >> 1; j > 0; j >>= 1) {
+      const bool flip = j == (k >> 1);  // the first step of a stage pairs i with its mirror in the block of k
+      for (unsigned long long t = (unsigned long long)tid; t < (k >> 1) * ((unsigned long long)M / k + 1);
+           t += kSelBlock) {
+        const unsigned long long i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        const unsigned long long l = flip ? (i ^ (k - 1)) : (i | j);
+        if (l >= (unsigned long long)M) continue;  // (i < l)
+        const unsigned long long ki = skey[i], kl = skey[l];
+        const int xi = sidx[i], xl = sidx[l];
+        if (ki > kl || (ki == kl && xi > xl)) {
+          skey[i] = kl;
+          skey[l] = ki;
+          sidx[i] = xl;
+          sidx[l] = xi;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  const int nv = min(M, a.budget[r]);
+  for (int k = tid; k < nv; k += kSelBlock) {
+    const int i = sidx[k];
+    const int e = (int)nev[i];
+    const CosRec c = rec[e];
+    ksim_cos_victim v;
+    v.event = e;
+    v.node = i;
+    v.gpu_mask = c.gpu_mask;
+    v.reserved = 0;
+    v.gpu_left_milli = (long long)(kMaxGpu * kMilli) - (long long)(skey[k] >> 32);
+    v.similarity = c.sim;
+    vict[k] = v;
   }
   if (tid == 0) a.n_vict[r] = nv;
 }

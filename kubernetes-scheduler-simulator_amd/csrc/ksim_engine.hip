@@ -1823,6 +1823,7 @@ struct HMemoState {  // k_hmemo (the keys in HBM)
 // every buffer and event used on them.  Before that the destructor sets the device, drains the side streams and then
 // the engine's (no dispatch, or a profiler's completion callback on it, may outlive its buffers, streams or graph),
 // destroys the graph and the communicator, and closes the peers' IPC-opened buffers.
+enum DsPlan { kDsNone, kDsFrag, kDsCos };  // the descheduling plan an engine holds
 struct ksim_engine {
   int device = 0;
   static constexpr int kSide = kSideStreams;
@@ -1955,7 +1956,7 @@ struct ksim_engine {
   // descheduling plan (ksim_engine_deschedule): made from the results and final node records of the last
   // completed run; per-event buffers at each replica's offset ds_eoff[r]
   bool ran = false;      // a ksim_engine_run completed since the last set_nodes / set_typical / load_events
-  bool ds_done = false;  // a plan of that run is held
+  DsPlan ds_plan = kDsNone;  // which plan of that run is held: an engine holds one
   DevBuf<ksim_ds::EvalRec> d_ds_eval;
   DevBuf<uint8_t> d_ds_gone;
   DevBuf<int32_t> d_ds_plist;
@@ -1963,6 +1964,9 @@ struct ksim_engine {
   DevBuf<int32_t> d_ds_cnt;    // [3][R] bound pods, budget, victims
   DevBuf<long long> d_ds_eoff;
   DevBuf<uint8_t> d_ds_tab;    // k_desched_select's per-node tables when they do not fit in LDS
+  DevBuf<ksim_ds::CosRec> d_ds_cos;         // cosSim (ksim_engine_deschedule_cossim): per-event records,
+  DevBuf<ksim_cos_victim> d_ds_cvict;       // victims,
+  DevBuf<uint8_t> d_ds_ctab;                // and k_cos_select's per-node tables beyond LDS
   std::vector<long long> ds_eoff;
   std::vector<int32_t> ds_budget, ds_nv;
   DevEvent ev_ds0, ev_ds1;
@@ -2798,7 +2802,8 @@ int ksim_engine_set_nodes(ksim_engine* e, int replica, const ksim_node* nodes) {
   e->h_nodes[replica].assign(nodes, nodes + e->N);
   e->h_rec[replica] = h;
   e->mplan_dirty = true;  // k_hmemo's plan holds the distinct initial node states
-  e->ran = e->ds_done = false;
+  e->ran = false;
+  e->ds_plan = kDsNone;
   e->total_gpus[replica] = gpus;
   KSIM_HIP(hipSetDevice(e->device));
   KSIM_HIP(hipMemcpyAsync(e->d_cap.p + (size_t)replica * e->N, cap.data(), sizeof(int32_t) * e->N, hipMemcpyHostToDevice,
@@ -2852,7 +2857,8 @@ int ksim_engine_set_typical(ksim_engine* e, int replica, const ksim_typical* tp,
   e->reps[replica].typed = typed ? 1 : 0;
   e->h_tp[replica] = h;
   e->mplan_dirty = true;  // k_hmemo's plan holds per-model views of the table
-  e->ran = e->ds_done = false;
+  e->ran = false;
+  e->ds_plan = kDsNone;
   int rc = upload_reps(e);
   if (rc) return rc;
   KSIM_HIP(hipStreamSynchronize(e->stream));
@@ -3087,7 +3093,8 @@ int ksim_engine_bind(ksim_engine* e, int replica, const ksim_pod* pod, int node,
 int ksim_engine_load_events(ksim_engine* e, int replica, const ksim_pod* events, int n) {
   if (e) e->mplan_dirty = true;
   if (!e || replica < 0 || replica >= e->R || n < 0 || (n > 0 && !events)) return KSIM_EINVAL;
-  e->ran = e->ds_done = false;
+  e->ran = false;
+  e->ds_plan = kDsNone;
   std::vector<PodDev> h(n);
   std::vector<char> gone(std::max(n, 1), 0);  // creations already deleted (the reference deletes a pod once)
   for (int i = 0; i < n; ++i) {
@@ -3946,7 +3953,8 @@ int ksim_engine_run(ksim_engine* e) {
   KSIM_HIP(hipSetDevice(e->device));
   const RunEnv env = read_env();
   e->report_done = false;
-  e->ran = e->ds_done = false;
+  e->ran = false;
+  e->ds_plan = kDsNone;
   e->grp_rev_used = 0;
   e->tev_used = 0u;  // KSIM_GROUP_TIMES: only run_persistent's concurrent groups record side-stream ends
   e->last_launches = 0;
@@ -4694,7 +4702,7 @@ int ksim_engine_deschedule(ksim_engine* e, int policy, double ratio) {
   if (!(ratio >= 0.0)) return KSIM_EINVAL;  // negative or NaN
   if (e->shard_world > 0) return KSIM_ENOTSUP;
   if (!e->ran) return KSIM_ESTATE;
-  e->ds_done = false;
+  e->ds_plan = kDsNone;
   KSIM_HIP(hipSetDevice(e->device));
   const int R = e->R;
   int max_ev = 0;
@@ -4756,13 +4764,13 @@ int ksim_engine_deschedule(ksim_engine* e, int policy, double ratio) {
   float ms = 0;
   KSIM_HIP(hipEventElapsedTime(&ms, e->ev_ds0, e->ev_ds1));
   e->last_ds_ms = ms;
-  e->ds_done = true;
+  e->ds_plan = kDsFrag;
   return KSIM_OK;
 }
 
 int ksim_engine_get_victims(ksim_engine* e, int replica, ksim_victim* out, int cap, int* n_out, int* budget_out) {
   if (!e || replica < 0 || replica >= e->R || cap < 0 || !n_out) return KSIM_EINVAL;
-  if (!e->ds_done) return KSIM_ESTATE;
+  if (e->ds_plan != kDsFrag) return KSIM_ESTATE;
   const int n = e->ds_nv[replica];
   *n_out = n;
   if (budget_out) *budget_out = e->ds_budget[replica];
@@ -4772,6 +4780,101 @@ int ksim_engine_get_victims(ksim_engine* e, int replica, ksim_victim* out, int c
   KSIM_HIP(hipSetDevice(e->device));
   KSIM_HIP(hipMemcpyAsync(out, e->d_ds_vict.p + e->ds_eoff[replica], sizeof(ksim_victim) * n, hipMemcpyDeviceToHost,
                           e->stream));
+  KSIM_HIP(hipStreamSynchronize(e->stream));
+  return KSIM_OK;
+}
+
+// The cosSim plan of every replica (ksim_desched.hpp): mark, evaluate, the budgets on the host from the bound-pod
+// counts, select.
+int ksim_engine_deschedule_cossim(ksim_engine* e, double ratio, int64_t cpu_bar_milli, int64_t gpu_bar_milli) {
+  if (check_gfx950(e ? e->device : 0)) return KSIM_ENODEV;
+  if (!e) return KSIM_EINVAL;
+  if (!(ratio >= 0.0) || cpu_bar_milli < 0 || gpu_bar_milli < 0) return KSIM_EINVAL;
+  if (e->shard_world > 0) return KSIM_ENOTSUP;
+  if (!e->ran) return KSIM_ESTATE;
+  e->ds_plan = kDsNone;
+  KSIM_HIP(hipSetDevice(e->device));
+  const int R = e->R;
+  int max_ev = 0;
+  e->ds_eoff.assign((size_t)R + 1, 0);
+  for (int r = 0; r < R; ++r) {
+    e->ds_eoff[r + 1] = e->ds_eoff[r] + e->n_events[r];
+    max_ev = std::max(max_ev, e->n_events[r]);
+  }
+  const size_t tot = (size_t)e->ds_eoff[R];
+  int rc = e->d_ds_cos.ensure(tot);
+  if (!rc) rc = e->d_ds_gone.ensure(tot);
+  if (!rc) rc = e->d_ds_cvict.ensure(tot);
+  if (!rc) rc = e->d_ds_cnt.ensure((size_t)3 * R);
+  if (!rc) rc = e->d_ds_eoff.upload(e->ds_eoff, e->stream);
+  const size_t tab = (size_t)e->N * ksim_ds::kCosNodeBytes;
+  const bool in_lds = tab <= (size_t)ksim_ds::kSelLdsBytes;
+  if (!rc && !in_lds) rc = e->d_ds_ctab.ensure(ksim_ds::cos_tab_stride(e->N) * R);
+  if (rc) return rc;
+  if (e->ev_ds0.ensure() || e->ev_ds1.ensure()) return KSIM_EHIP;
+  ksim_ds::DsArgs m = {};  // k_desched_mark reads reps, eoff and gone
+  m.reps = e->d_reps.p;
+  m.eoff = e->d_ds_eoff.p;
+  m.gone = e->d_ds_gone.p;
+  m.N = e->N;
+  ksim_ds::CosArgs a;
+  a.reps = e->d_reps.p;
+  a.eoff = e->d_ds_eoff.p;
+  a.rec = e->d_ds_cos.p;
+  a.gone = e->d_ds_gone.p;
+  a.vict = e->d_ds_cvict.p;
+  a.bound = e->d_ds_cnt.p;
+  a.budget = e->d_ds_cnt.p + R;
+  a.n_vict = e->d_ds_cnt.p + 2 * R;
+  a.tab = in_lds ? nullptr : e->d_ds_ctab.p;
+  a.cpu_bar = (long long)cpu_bar_milli;
+  a.gpu_bar = (long long)gpu_bar_milli;
+  a.N = e->N;
+  KSIM_HIP(hipEventRecord(e->ev_ds0, e->stream));
+  if (tot) KSIM_HIP(hipMemsetAsync(e->d_ds_gone.p, 0, tot, e->stream));
+  KSIM_HIP(hipMemsetAsync(e->d_ds_cnt.p, 0, sizeof(int32_t) * 3 * R, e->stream));
+  if (max_ev > 0) {
+    const dim3 grid((unsigned)((max_ev + ksim_ds::kEvalBlock - 1) / ksim_ds::kEvalBlock), (unsigned)R);
+    hipLaunchKernelGGL(ksim_ds::k_desched_mark, grid, dim3(ksim_ds::kEvalBlock), 0, e->stream, m);
+    KSIM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ksim_ds::k_cos_eval, grid, dim3(ksim_ds::kEvalBlock), 0, e->stream, a);
+    KSIM_HIP(hipGetLastError());
+  }
+  std::vector<int32_t> bound((size_t)R, 0);
+  KSIM_HIP(hipMemcpyAsync(bound.data(), a.bound, sizeof(int32_t) * R, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipStreamSynchronize(e->stream));
+  // deschedule.go:27 int(math.Ceil(ratio * float64(len(podMap)))); never more than the pods there are
+  e->ds_budget.assign((size_t)R, 0);
+  for (int r = 0; r < R; ++r)
+    e->ds_budget[r] = (int32_t)std::min(std::ceil(ratio * (double)bound[r]), (double)bound[r]);
+  KSIM_HIP(hipMemcpyAsync(e->d_ds_cnt.p + R, e->ds_budget.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(ksim_ds::k_cos_select, dim3((unsigned)R), dim3(ksim_ds::kSelBlock), in_lds ? tab : (size_t)0,
+                     e->stream, a);
+  KSIM_HIP(hipGetLastError());
+  e->ds_nv.assign((size_t)R, 0);
+  KSIM_HIP(hipMemcpyAsync(e->ds_nv.data(), a.n_vict, sizeof(int32_t) * R, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipEventRecord(e->ev_ds1, e->stream));
+  KSIM_HIP(hipStreamSynchronize(e->stream));
+  float ms = 0;
+  KSIM_HIP(hipEventElapsedTime(&ms, e->ev_ds0, e->ev_ds1));
+  e->last_ds_ms = ms;
+  e->ds_plan = kDsCos;
+  return KSIM_OK;
+}
+
+int ksim_engine_get_cos_victims(ksim_engine* e, int replica, ksim_cos_victim* out, int cap, int* n_out,
+                                int* budget_out) {
+  if (!e || replica < 0 || replica >= e->R || cap < 0 || !n_out) return KSIM_EINVAL;
+  if (e->ds_plan != kDsCos) return KSIM_ESTATE;
+  const int n = e->ds_nv[replica];
+  *n_out = n;
+  if (budget_out) *budget_out = e->ds_budget[replica];
+  if (cap < n) return KSIM_ERANGE;
+  if (n == 0) return KSIM_OK;
+  if (!out) return KSIM_EINVAL;
+  KSIM_HIP(hipSetDevice(e->device));
+  KSIM_HIP(hipMemcpyAsync(out, e->d_ds_cvict.p + e->ds_eoff[replica], sizeof(ksim_cos_victim) * n,
+                          hipMemcpyDeviceToHost, e->stream));
   KSIM_HIP(hipStreamSynchronize(e->stream));
   return KSIM_OK;
 }

@@ -134,11 +134,20 @@ class Victim(C.Structure):
                 ("score", C.c_int64), ("frag_before", C.c_double), ("frag_after", C.c_double)]
 
 
-# deschedule.go:14-17 descheduleConfig.policy
+class CosVictim(C.Structure):
+    """ksim_cos_victim: one pod of a cosSim plan (Engine.deschedule_cossim / Engine.cos_victims)."""
+    _fields_ = [("event", C.c_int32), ("node", C.c_int32), ("gpu_mask", C.c_int32), ("reserved", C.c_int32),
+                ("gpu_left_milli", C.c_int64), ("similarity", C.c_double)]
+
+
+# deschedule.go:14-17 descheduleConfig.policy (cosSim has entry points of its own: Engine.deschedule_cossim)
 DESCHED_POLICY = {"fragOnePod": 0, "fragMultiPod": 1}
+# deschedule.go:52-53: the reference's hard-coded milliCpuBar / milliGpuBar
+COS_CPU_BAR_MILLI, COS_GPU_BAR_MILLI = 2000, 500
 
 assert C.sizeof(Node) == 128 and C.sizeof(Pod) == 48 and C.sizeof(Typical) == 32 and C.sizeof(Result) == 24
 assert C.sizeof(Report) == 112 and C.sizeof(PowerReport) == 32 and C.sizeof(Victim) == 40
+assert C.sizeof(CosVictim) == 32
 
 _LIB = None
 
@@ -207,6 +216,8 @@ SIGNATURES = {
     "ksim_engine_deschedule": (C.c_int, [_VP, C.c_int, C.c_double]),
     "ksim_engine_get_victims": (C.c_int, [_VP, C.c_int, _P(Victim), C.c_int, _P(C.c_int), _P(C.c_int)]),
     "ksim_engine_last_deschedule_ms": (C.c_int, [_VP, _P(C.c_double)]),
+    "ksim_engine_deschedule_cossim": (C.c_int, [_VP, C.c_double, C.c_int64, C.c_int64]),
+    "ksim_engine_get_cos_victims": (C.c_int, [_VP, C.c_int, _P(CosVictim), C.c_int, _P(C.c_int), _P(C.c_int)]),
 }
 
 
@@ -751,6 +762,26 @@ class Engine:
             check(rc, "get_victims")
         out = (Victim * max(1, n.value))()
         check(lib().ksim_engine_get_victims(self.h, r, out, n.value, C.byref(n), C.byref(budget)), "get_victims")
+        return [out[i] for i in range(n.value)], budget.value
+
+    def deschedule_cossim(self, ratio, cpu_bar=COS_CPU_BAR_MILLI, gpu_bar=COS_GPU_BAR_MILLI):
+        """Plan by the cosSim policy (deschedule.go:49-92): on every node with less than cpu_bar milli-CPU left
+        and a GPU with more than gpu_bar milli left, the bound pod least aligned with what the node has left.
+        The defaults are the values the reference hard-codes.  Changes no cluster state; returns the plan's
+        device time in ms."""
+        check(lib().ksim_engine_deschedule_cossim(self.h, float(ratio), int(cpu_bar), int(gpu_bar)),
+              "deschedule_cossim")
+        return self.last_deschedule_ms()
+
+    def cos_victims(self, r):
+        """(victims of replica r's cosSim plan in eviction order, budget): a list of CosVictim and an int."""
+        n, budget = C.c_int(0), C.c_int(0)
+        rc = lib().ksim_engine_get_cos_victims(self.h, r, None, 0, C.byref(n), C.byref(budget))
+        if rc != KSIM_ERANGE:
+            check(rc, "get_cos_victims")
+        out = (CosVictim * max(1, n.value))()
+        check(lib().ksim_engine_get_cos_victims(self.h, r, out, n.value, C.byref(n), C.byref(budget)),
+              "get_cos_victims")
         return [out[i] for i in range(n.value)], budget.value
 
     def last_deschedule_ms(self):

@@ -169,6 +169,27 @@ def failed_pods_messages(failed):
     return ["Failed Pods in detail:\n"] + ["  %s: %s\n" % (k, r) for k, r in failed] + [""]
 
 
+def _is_delete(ev):
+    return bool(ev["is_delete"] if isinstance(ev, dict) or hasattr(ev, "dtype") else ev.is_delete)
+
+
+def _write_event(f, i, rep, key=None, is_del=False, pod=None, status=None, power=None, failed=None):
+    """One pod event as SchedulePods logs it (simulator.go:405-428): the attempt line, the pod's
+    Characteristics, the failure line, the cluster report and the [Power] line."""
+    if key is not None:
+        f.write(logrus_line("[%d] attempt to %s pod(%s)\n" % (i, "delete" if is_del else "create", key)))
+        if not is_del and pod is not None:
+            f.write(logrus_line("Characteristics of pod(%s): %s\n" % (key, pod_repr(*pod))))
+        if not is_del and status in (1, 2):
+            rp = pod_repr(*pod) if pod is not None else ""
+            f.write(logrus_line("[%d] failed to schedule pod(%s): %s\n" % (i, key, rp)))
+            failed.append((key, rp))
+    for m in report_messages(rep):
+        f.write(logrus_line(m))
+    if power is not None:
+        f.write(logrus_line(power_message(power)))
+
+
 def write_log(path, reports, pod_names=None, events=None, power=None, pods=None, results=None, final_nodes=None,
               n_original=None, tag="InitSchedule"):
     """A log file as `simon apply` writes it, with the lines the reference's harness reads:
@@ -185,21 +206,10 @@ def write_log(path, reports, pod_names=None, events=None, power=None, pods=None,
     with open(path, "w") as f:
         f.write(logrus_line("Number of original workload pods: %d" % n0))
         for i, rep in enumerate(reports):
-            is_del = events is not None and bool(events[i]["is_delete"] if isinstance(events[i], dict) or
-                                                  hasattr(events[i], "dtype") else events[i].is_delete)
-            if pod_names is not None:
-                key = pod_names[i]
-                f.write(logrus_line("[%d] attempt to %s pod(%s)\n" % (i, "delete" if is_del else "create", key)))
-                if not is_del and pods is not None:
-                    f.write(logrus_line("Characteristics of pod(%s): %s\n" % (key, pod_repr(*pods[i]))))
-                if not is_del and results is not None and results[i] in (1, 2):
-                    rp = pod_repr(*pods[i]) if pods is not None else ""
-                    f.write(logrus_line("[%d] failed to schedule pod(%s): %s\n" % (i, key, rp)))
-                    failed.append((key, rp))
-            for m in report_messages(rep):
-                f.write(logrus_line(m))
-            if power is not None:
-                f.write(logrus_line(power_message(power[i])))
+            _write_event(f, i, rep, key=None if pod_names is None else pod_names[i],
+                         is_del=events is not None and _is_delete(events[i]), pod=None if pods is None else pods[i],
+                         status=None if results is None else results[i], power=None if power is None else power[i],
+                         failed=failed)
         if final_nodes is not None:
             for m in failed_pods_messages(failed):
                 f.write(logrus_line(m))
@@ -207,6 +217,67 @@ def write_log(path, reports, pod_names=None, events=None, power=None, pods=None,
                 f.write(logrus_line(m))
             if failed:
                 f.write(logrus_line("there are %d unscheduled pods\n" % len(failed)))
+
+
+def write_desched_log(path, reports, victim_events, policy, budget, stage_nodes, pod_names=None, events=None,
+                      power=None, pods=None, results=None, n_original=None):
+    """The log of a run with a descheduling stage (core.go:213-218, deschedule.go:20-47), all three policies.
+    reports / power / results cover the extended stream of ksim.desched.run: the n original events, one delete
+    event per victim, one re-creation per victim; pod_names / pods / events cover the original events, and
+    victim_events names the victims' creation events in eviction order.  stage_nodes: the final-node dicts of
+    cluster_analysis_messages at the three stage ends, keyed InitSchedule / PostEviction / PostDeschedule.
+    After the InitSchedule part that write_log writes (core.go:156-157), in the reference's order:
+      "maximum number of pods that can be descheduled: B, deschedule policy: P" (deschedule.go:28);
+      the evictions are silent (deletePod is not SchedulePods: no per-event lines);
+      ClusterAnalysis(PostEviction), its fragmentation bins the report row of the last eviction;
+      "[DescheduleCluster] Num of Descheduled Pods: V";
+      SchedulePods of the victims (simulator.go:377-433): the index restarts at 0 and so do the arrived
+        counters (:384-385), so Arrived GPU / CPU Milli count from the stage's start;
+      "[DescheduleCluster] Num of Failed Pods: F" (deschedule.go:45);
+      ClusterAnalysis(PostDeschedule) and one more ClusterGpuFragReport (core.go:217-218: no [Power] line);
+      "there are N unscheduled pods" over both stages (apply.go:228-229)."""
+    nv = len(victim_events)
+    n = len(reports) - 2 * nv
+    if n < 1:
+        raise ValueError("a descheduling log needs at least one original event")
+    n0 = n_original if n_original is not None else (n if pod_names is None else len(set(pod_names)))
+    failed = []
+    base_gpu, base_cpu = reports[n - 1]["arrived_gpu_milli"], reports[n - 1]["arrived_cpu_milli"]
+
+    def staged(rep):  # the report with the stage's own arrived counters
+        return dict(rep, arrived_gpu_milli=rep["arrived_gpu_milli"] - base_gpu,
+                    arrived_cpu_milli=rep["arrived_cpu_milli"] - base_cpu)
+
+    with open(path, "w") as f:
+        f.write(logrus_line("Number of original workload pods: %d" % n0))
+        for i in range(n):
+            _write_event(f, i, reports[i], key=None if pod_names is None else pod_names[i],
+                         is_del=events is not None and _is_delete(events[i]), pod=None if pods is None else pods[i],
+                         status=None if results is None else results[i], power=None if power is None else power[i],
+                         failed=failed)
+        for m in failed_pods_messages(failed):
+            f.write(logrus_line(m))
+        for m in cluster_analysis_messages(stage_nodes["InitSchedule"], reports[n - 1]["frag_bins"], "InitSchedule"):
+            f.write(logrus_line(m))
+        f.write(logrus_line("maximum number of pods that can be descheduled: %d, deschedule policy: %s\n"
+                            % (budget, policy)))
+        for m in cluster_analysis_messages(stage_nodes["PostEviction"], reports[n + nv - 1]["frag_bins"],
+                                           "PostEviction"):
+            f.write(logrus_line(m))
+        f.write(logrus_line("[DescheduleCluster] Num of Descheduled Pods: %d\n" % nv))
+        n_init_failed = len(failed)
+        for k, e in enumerate(victim_events):
+            i = n + nv + k
+            _write_event(f, k, staged(reports[i]), key=None if pod_names is None else pod_names[e],
+                         pod=None if pods is None else pods[e], status=None if results is None else results[i],
+                         power=None if power is None else power[i], failed=failed)
+        f.write(logrus_line("[DescheduleCluster] Num of Failed Pods: %d\n" % (len(failed) - n_init_failed)))
+        for m in cluster_analysis_messages(stage_nodes["PostDeschedule"], reports[-1]["frag_bins"], "PostDeschedule"):
+            f.write(logrus_line(m))
+        for m in report_messages(staged(reports[-1])):
+            f.write(logrus_line(m))
+        if failed:
+            f.write(logrus_line("there are %d unscheduled pods\n" % len(failed)))
 
 
 def parse_log_lines(lines):
