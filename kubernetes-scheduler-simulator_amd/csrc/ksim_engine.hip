@@ -57,7 +57,7 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kNBMax = 64;
 constexpr int kMaxCand = 9;
-constexpr int kTagStride = 16;
+constexpr int kTagStride = ksim_plan::replay::kTagStride;
 
 struct StepArgs {
   ReplicaDev* reps;
@@ -2394,7 +2394,7 @@ static int launch_memo(ksim_engine* e, const RunEnv& env, const MemoPlan& pl, in
     KSIM_HIP(hipMemsetAsync(e->d_prof.p, 0, sizeof(unsigned long long) * (size_t)pl.nwg * ksim_memo::kProfPhases, st));
     ma.prof = e->d_prof.p;
   }
-  const bool any_delete = std::any_of(e->memo.reps.begin(), e->memo.reps.end(), [&](int r) { return (bool)e->has_delete[r]; });
+  const bool any_delete = std::any_of(e->memo.reps.begin(), e->memo.reps.end(), [&](int r) { return e->has_delete[r] != 0; });
   const void* f = memo_kernel(memo_form(pl.decider, pl.hkeys, profile, tracing, e->d_th.p != nullptr, any_delete, e->report,
                                         ma.delay));
   const TypDev* tpp = e->d_tp.p;
@@ -3364,23 +3364,6 @@ static void print_replay_profile(ksim_engine* e, int R, int K, int steps) {
   std::fprintf(stderr, "\n");
 }
 
-// Workgroups per replica for k_replay: every workgroup of a launch must be
-// co-resident (they exchange granules every step), so R*K never exceeds one
-// workgroup per CU; K = 1 needs no co-residency at all.
-static int choose_wgs(const ksim_engine* e, int R) {
-  // auto: one workgroup per CU up to 64 per replica; large clusters (C5: 100k nodes) go wider
-  // so that a slice stays near 384 nodes (one to two FGD evaluation rounds per step)
-  int K = e->wgs_req;
-  if (K <= 0) {
-    K = std::min(e->cus / R, 64);
-    K = std::max(K, std::min(e->cus / R, (e->N + 383) / 384));
-  }
-  K = std::max(1, std::min(K, ksim_replay::kMaxK));
-  K = std::min(K, e->N);
-  if (R * K > e->cus) K = 1;
-  return K;
-}
-
 static int resident_cap(const ksim_engine* e, const void* f, size_t lds) {
   (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   int nb = 0;
@@ -3389,10 +3372,6 @@ static int resident_cap(const ksim_engine* e, const void* f, size_t lds) {
     nb = 0;
   }
   return nb * e->cus;
-}
-
-static size_t replay_lds(int S, int pol, bool general) {  // S real slots + the virtual node
-  return ksim_replay::replay_layout(S, pol, general).total;
 }
 
 // The dead-class skip (k_memo, k_hmemo, k_scan1): on create-only streams a class that once found no
@@ -3406,10 +3385,6 @@ static bool dead_skip(const ksim_engine* e, const RunEnv& env, const std::vector
   return true;
 }
 
-// Group kinds of a run beside the policies themselves
-constexpr int kPolRandomGo = 64;  // run_persistent's group id of the k_random_go replicas
-constexpr int kPolFgdH = 66;      // ... of the one-workgroup FGD replicas on k_hmemo beside wide ones on k_memo (split_fgd)
-
 static void note_kernel(ksim_engine* e, const char* name) {
   for (size_t p = 0; p < e->last_kernels.size();) {  // each name once
     size_t q = e->last_kernels.find('+', p);
@@ -3421,171 +3396,28 @@ static void note_kernel(ksim_engine* e, const char* name) {
   e->last_kernels += name;
 }
 
-// ---- the run plan: everything run_persistent decides, before it launches anything ----
-enum GroupKernel { kRunRandomGo, kRunScan1, kRunMemo, kRunHmemo, kRunReplay, kRunNone };
-
-struct PlanGroup {
-  int kind = 0;              // a policy, kPolFgdH, ksim_scan1::kPolMix or kPolRandomGo
-  int first = 0, count = 0;  // its replicas: RunPlan::order[first .. first + count)
-  GroupKernel kernel = kRunReplay;  // (kRunNone: an FGD group the required memoised kernel has no plan for)
-  int side = -1;             // its side stream's index; -1: the engine stream
-  int K = 1, S = 0;          // k_replay and k_scan1 groups: workgroups per replica, nodes per slice, dynamic LDS bytes
-  size_t lds = 0;            // (k_replay: a co-resident grid the device cannot hold is narrowed at launch)
-};
-
-struct RunPlan {
-  std::vector<int> order;  // the replicas in launch order (uploaded as d_replist)
-  std::vector<PlanGroup> groups;
-  bool any_delete = false, general = false;  // general: k_replay's instantiation with timers, report stores, deletes
-  bool concurrent = false;                   // the groups on side streams, else back to back on the engine stream
-  bool reg1 = false;                         // k_scan1 keeps the node records in VGPRs
-  int fgd_cus = 0;                           // CUs the FGD groups hold (a k_memo / k_hmemo workgroup fills a CU's registers)
-};
-
-// K, S and LDS bytes of a k_replay group: choose_wgs, then narrower slices until the layout fits in LDS (or cannot
-// be narrowed further: the launcher refuses a layout that still does not fit).  Returns choose_wgs' own K.
-static int replay_fit(const ksim_engine* e, bool general, PlanGroup& g) {
-  const int K0 = g.K = choose_wgs(e, g.count);
-  g.S = (e->N + g.K - 1) / g.K;
-  while (replay_lds(g.S, g.kind, general) > 160 * 1024 && g.K < ksim_replay::kMaxK && g.count * (g.K + 1) <= e->cus) {
-    ++g.K;
-    g.S = (e->N + g.K - 1) / g.K;
-  }
-  g.lds = replay_lds(g.S, g.kind, general);
-  return K0;
-}
-
-// The replicas ordered into groups: a split FGD run's two plans first, then one group per policy present, the
-// Random replicas on Go's stream last (one k_random_go workgroup each).
-static void plan_order(const ksim_engine* e, RunPlan& pl) {
-  auto add = [&](int kind, int count) {
-    PlanGroup g;
-    g.kind = kind;
-    g.count = count;
-    if (count) pl.groups.push_back(g);
-  };
-  if (e->split_fgd) {  // the wide FGD replicas (k_memo) first, then the one-workgroup ones (k_hmemo): the plans' orders
-    pl.order = e->memo.reps;
-    pl.order.insert(pl.order.end(), e->hmemo.reps.begin(), e->hmemo.reps.end());
-    add(POL_FGD, (int)e->memo.reps.size());
-    add(kPolFgdH, (int)e->hmemo.reps.size());
-  }
-  for (int pol = e->split_fgd ? POL_BESTFIT : POL_FGD; pol <= POL_PWR_FGD; ++pol) {
-    int c = 0;
-    for (int r = 0; r < e->R; ++r)
-      if (e->reps[r].policy == pol && !go_random(e, r)) { pl.order.push_back(r); ++c; }
-    add(pol, c);
-  }
-  int c = 0;
+// What the run planner (ksim_plan.hpp make_run_plan) reads of the engine, once prepare_memo has made the FGD plans.
+static RunPlanInput run_plan_input(const ksim_engine* e, const RunEnv& env) {
+  RunPlanInput in;
   for (int r = 0; r < e->R; ++r)
-    if (go_random(e, r)) { pl.order.push_back(r); ++c; }
-  add(kPolRandomGo, c);
-}
-
-// Each group's kernel (with the k_replay fit of those that have no other), and whether the groups run concurrently on
-// side streams: when every group is at ONE workgroup per replica (no cross-workgroup exchange, so no co-residency
-// needed; a paper-sweep group fills 170 of 256 CUs, the next group's workgroups take the rest).  A group needing K > 1,
-// a k_memo launch outside a split FGD run or the profile timers keep the launches back to back on the engine stream.
-static void plan_kernels(const ksim_engine* e, const RunEnv& env, RunPlan& pl) {
-  const bool profile = env.timers();
-  pl.concurrent = !profile && pl.groups.size() >= 2;
-  for (PlanGroup& g : pl.groups) {
-    const bool fgd = g.kind == POL_FGD && e->run_mode != 2;
-    if (g.kind == kPolRandomGo) {  // one workgroup per replica
-      g.kernel = kRunRandomGo;
-    } else if (fgd && e->memo.ok) {  // (a split FGD run's wide group is launched first, behind its gate)
-      g.kernel = kRunMemo;
-      pl.concurrent = pl.concurrent && e->split_fgd;
-    } else if ((fgd || g.kind == kPolFgdH) && e->hmemo.ok) {  // concurrent at one workgroup per replica
-      g.kernel = kRunHmemo;
-      pl.concurrent = pl.concurrent && (g.kind == kPolFgdH || e->hmemo.plan.K == 1);
-    } else {
-      const int K0 = replay_fit(e, pl.general, g);
-      if (g.kind != kPolFgdH) pl.concurrent = pl.concurrent && g.K == 1;
-      // one workgroup per replica, create-only, a cheap policy: the 256-thread k_scan1 (ksim_scan1.hpp)
-      const bool scan1 = K0 == 1 && !profile && !pl.any_delete && e->scan1 && e->N <= kMaxSlice &&
-                         scan1_fn(g.kind, e->report, pl.reg1) &&
-                         ksim_scan1::scan1_lds(e->N, g.kind, e->report, pl.reg1) <= 160 * 1024;
-      if ((fgd || g.kind == kPolFgdH) && e->run_mode >= 3 && e->run_mode <= 5) {
-        g.kernel = kRunNone;
-      } else if (scan1) {
-        g.kernel = kRunScan1;
-        g.K = 1;
-        g.S = e->N;
-        g.lds = ksim_scan1::scan1_lds(e->N, g.kind, e->report, pl.reg1);
-      }
-    }
-  }
-}
-
-// The cheap-policy groups a concurrent run would give one k_scan1 launch each become ONE k_scan1_mix launch (policy
-// per workgroup), its replicas longest stream first, where the first of them stood: the run then needs one side
-// stream beside the FGD group's, whatever the hardware-queue mapping of the process.
-static void plan_mix(const ksim_engine* e, const RunEnv& env, RunPlan& pl) {
-  if (!(pl.concurrent && !pl.any_delete && e->scan1 && e->N <= kMaxSlice && env.scan1_mix &&
-        ksim_scan1::scan1_lds(e->N, ksim_scan1::kPolMix, e->report, pl.reg1) <= 160 * 1024))
-    return;
-  std::vector<int> mix, norder;
-  std::vector<PlanGroup> ngroups;
-  int f = 0, at = -1, nmix = 0;
-  for (const PlanGroup& g : pl.groups) {
-    bool m = g.kind >= POL_BESTFIT && g.kind <= POL_RANDOM;
-    for (int j = f; m && j < f + g.count; ++j)
-      m = g.kind != POL_DOTPROD || e->reps[pl.order[j]].dpcfg == (DIM_MERGE | NORM_MAX << 4);
-    if (m) {
-      mix.insert(mix.end(), pl.order.begin() + f, pl.order.begin() + f + g.count);
-      if (at < 0) at = (int)ngroups.size();
-      ++nmix;
-    } else {
-      ngroups.push_back(g);
-      norder.insert(norder.end(), pl.order.begin() + f, pl.order.begin() + f + g.count);
-    }
-    f += g.count;
-  }
-  if (nmix < 2) return;
-  std::stable_sort(mix.begin(), mix.end(), [&](int x, int y) { return e->n_events[x] > e->n_events[y]; });
-  int off = 0;
-  for (int g = 0; g < at; ++g) off += ngroups[g].count;
-  norder.insert(norder.begin() + off, mix.begin(), mix.end());
-  PlanGroup mg;
-  mg.kind = ksim_scan1::kPolMix;
-  mg.count = (int)mix.size();
-  mg.kernel = kRunScan1;
-  mg.K = 1;
-  mg.S = e->N;
-  mg.lds = ksim_scan1::scan1_lds(e->N, ksim_scan1::kPolMix, e->report, pl.reg1);
-  ngroups.insert(ngroups.begin() + at, mg);
-  pl.order.swap(norder);
-  pl.groups.swap(ngroups);
-}
-
-// What a run launches, in which order, on which streams.  Decides only: no launch, no engine state changed.
-static RunPlan make_run_plan(const ksim_engine* e, const RunEnv& env) {
-  RunPlan pl;
-  for (int r = 0; r < e->R; ++r) pl.any_delete = pl.any_delete || e->has_delete[r];
-  pl.general = env.timers() || e->report || pl.any_delete;
-  pl.reg1 = e->scan1 == 2 && e->N <= ksim_scan1::kBlock * ksim_scan1::kRegSlots;
-  plan_order(e, pl);
-  plan_kernels(e, env, pl);
-  plan_mix(e, env, pl);
-  // The side streams share the process's hardware queues (GPU_MAX_HW_QUEUES, HIP's default 4), and two streams on one
-  // queue run their kernels one after the other.  So no more side streams than queues (RunEnv::side_streams): the first
-  // group (FGD on k_hmemo, the longest in a paper sweep) gets one to itself, the others take the rest round robin.  A
-  // split FGD run's wide k_memo group runs on the engine stream itself, which otherwise only waits: three groups then
-  // need two side streams (with three, two groups shared a queue: 64 -> 133 ms for a C4 share, profiles/r06/c4_wide/).
-  const int nq = env.side_streams, g_off = e->split_fgd ? 1 : 0;
-  int first = 0;
-  for (int gi = 0; gi < (int)pl.groups.size(); ++gi) {
-    PlanGroup& g = pl.groups[gi];
-    g.first = first;
-    first += g.count;
-    const int j = gi - g_off;
-    g.side = !pl.concurrent || j < 0 ? -1 : (j == 0 || nq == 1) ? 0 : 1 + (j - 1) % (nq - 1);
-    if (g.kind == kPolFgdH) pl.fgd_cus += g.count;
-    else if (g.kind == POL_FGD && e->run_mode != 2)
-      pl.fgd_cus += e->memo.ok ? e->memo.plan.nwg : g.count * (e->hmemo.ok ? e->hmemo.plan.K : 1);
-  }
-  return pl;
+    in.reps.push_back({e->reps[r].policy, go_random(e, r), e->n_events[r], (bool)e->has_delete[r], e->reps[r].dpcfg});
+  in.N = e->N;
+  in.cus = e->cus;
+  in.wgs_req = e->wgs_req;
+  in.run_mode = e->run_mode;
+  in.report = e->report;
+  in.scan1 = e->scan1;
+  in.split_fgd = e->split_fgd;
+  in.memo_ok = e->memo.ok;
+  in.memo_nwg = e->memo.plan.nwg;
+  in.memo_reps = e->memo.reps;
+  in.hmemo_ok = e->hmemo.ok;
+  in.hmemo_K = e->hmemo.plan.K;
+  in.hmemo_reps = e->hmemo.reps;
+  in.timers = env.timers();
+  in.scan1_mix = env.scan1_mix;
+  in.side_streams = env.side_streams;
+  return in;
 }
 
 static hipStream_t group_stream(const ksim_engine* e, const PlanGroup& g) { return g.side < 0 ? e->stream : e->side[g.side]; }
@@ -3618,7 +3450,7 @@ static int upload_go_states(ksim_engine* e, const RunPlan& plan) {
 
 static int launch_random_go(ksim_engine* e, const PlanGroup& g, hipStream_t gs) {
   ksim_random_go::RandGoArgs ga{e->d_reps.p, e->d_replist.p + g.first, e->d_go.p, e->N};
-  const bool in_lds = ksim_random_go::lds_bytes(e->N, true) <= 160 * 1024;
+  const bool in_lds = ksim_random_go::lds_bytes(e->N, true) <= kLdsMax;
   const size_t lds = ksim_random_go::lds_bytes(e->N, in_lds);
   if (in_lds) {
     KSIM_HIP(hipFuncSetAttribute((const void*)ksim_random_go::k_random_go<true>,
@@ -3668,6 +3500,7 @@ static int launch_scan1(ksim_engine* e, const RunEnv& env, const RunPlan& plan, 
   const void* f = !mix ? scan1_fn(g.kind, e->report, reg)
                   : e->report ? (reg ? (const void*)k_scan1_mix<true, true> : (const void*)k_scan1_mix<true, false>)
                               : (reg ? (const void*)k_scan1_mix<false, true> : (const void*)k_scan1_mix<false, false>);
+  if (!f) return KSIM_ENOTSUP;  // scan1_serves (the planner) names a policy scan1_fn has no instantiation for
   Scan1Args sa{e->d_reps.p, e->d_replist.p + g.first, e->N, dead_skip(e, env, group_reps(plan, g)) ? 1 : 0, nullptr, 0};
   KSIM_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
   if (mix && plan.concurrent && e->report && gi > 0 && env.report_overlap) {
@@ -3752,11 +3585,36 @@ static int replay_pf_memo(const ksim_engine* e, const RunEnv& env, const RunPlan
   int pm_c = 0;
   for (int j = g.first; j < g.first + g.count; ++j) pm_c = std::max(pm_c, (int)e->h_cls[plan.order[j]].size());
   const size_t lm = ksim_replay::replay_layout(S, g.kind, plan.general, pm_c).total;
-  if (!(pm_c > 0 && lm <= 160 * 1024 &&
+  if (!(pm_c > 0 && lm <= kLdsMax &&
         (K == 1 || resident_cap(e, replay_kernel(g.kind, K, plan.general), lm) >= g.count * K)))
     return 0;
   *lds = lm;
   return pm_c;
+}
+
+// The arguments of a k_replay launch, every field: the lean defaults (no PWR+FGD memo, the guessed ranges learnt, no
+// profile buffer), which launch_replay overrides from the run's knobs.  xK > 0: a node-sharded group's launch
+// (run_replay_group), the exchange spanning xK columns.
+static ksim_replay::ReplayArgs replay_args(ReplicaDev* reps, const int* rep_list, int N, int K, int S,
+                                           unsigned long long* gran, int2* hist, int max_ev, int* fail, bool skip, int xK) {
+  ksim_replay::ReplayArgs ra;
+  ra.reps = reps;
+  ra.rep_list = rep_list;
+  ra.N = N;
+  ra.K = K;
+  ra.S = S;
+  ra.gran = gran;
+  ra.hist = hist;
+  ra.hist_stride = std::max(max_ev, 1);
+  ra.fail = fail;
+  ra.prof = nullptr;
+  ra.skip = skip ? 1 : 0;
+  ra.pm_c = 0;
+  ra.pm_ver0 = 0u;
+  ra.pf_guess = 1;
+  ra.xK = xK;
+  ra.group = xK > 0 ? 1 : 0;
+  return ra;
 }
 
 // k_replay: one launch per policy (the kernel is specialised on it), K workgroups per replica.
@@ -3765,40 +3623,27 @@ static int launch_replay(ksim_engine* e, const RunEnv& env, const RunPlan& plan,
   const int pol = g.kind, Rg = g.count;
   const bool general = plan.general, profile = env.timers();
   int K = g.K, S = g.S;
-  if (g.lds > 160 * 1024) return KSIM_ERANGE;
+  if (g.lds > kLdsMax) return KSIM_ERANGE;
   if (K > 1) {
     // the occupancy query bounds the co-resident grid: fewer, larger slices when it is short
     const int cap = resident_cap(e, replay_kernel(pol, K, general), g.lds);
-    if (Rg * K > cap) {
-      if (e->wgs_req > 0 && cap < Rg) return KSIM_ERANGE;
-      K = std::max(1, std::min(K, cap / Rg));
-      S = (e->N + K - 1) / K;
-      if (replay_lds(S, pol, general) > 160 * 1024) {
-        std::fprintf(stderr, "ksim: k_replay needs %d co-resident workgroups; the device holds %d\n", Rg * K, cap);
-        return KSIM_ERANGE;
-      }
-    }
+    const ReplayNarrow nw =
+        replay_narrow(K, cap, Rg, e->N, e->wgs_req, [&](int s) { return replay::replay_lds(s, pol, general); });
+    if (nw.refused == kNarrowLds)
+      std::fprintf(stderr, "ksim: k_replay needs %d co-resident workgroups; the device holds %d\n", Rg * nw.K, cap);
+    if (nw.refused != kNarrowOk) return KSIM_ERANGE;
+    K = nw.K;
+    S = nw.S;
   }
   int rc;
   if (plan.any_delete && (rc = e->d_hist.ensure((size_t)e->R * K * std::max(max_ev, 1)))) return rc;  // the bind history
-  size_t lds = replay_lds(S, pol, general);
-  ksim_replay::ReplayArgs ra;
-  ra.xK = 0;
-  ra.group = 0;
+  size_t lds = replay::replay_lds(S, pol, general);
+  ksim_replay::ReplayArgs ra = replay_args(e->d_reps.p, e->d_replist.p + g.first, e->N, K, S, e->d_gran.p,
+                                           plan.any_delete ? e->d_hist.p : nullptr, max_ev, e->d_fail.p,
+                                           dead_skip(e, env, group_reps(plan, g)), 0);
   ra.pm_c = e->last_pf_memo = replay_pf_memo(e, env, plan, g, K, S, &lds);
   ra.pm_ver0 = env.pf_memo_ver0 > 0 && env.pf_memo_ver0 < (long)ksim_replay::kPmInvalid ? (unsigned)env.pf_memo_ver0 : 0u;
   ra.pf_guess = env.pf_guess ? 1 : 0;
-  ra.reps = e->d_reps.p;
-  ra.rep_list = e->d_replist.p + g.first;
-  ra.N = e->N;
-  ra.K = K;
-  ra.S = S;
-  ra.gran = e->d_gran.p;
-  ra.hist = plan.any_delete ? e->d_hist.p : nullptr;
-  ra.hist_stride = std::max(max_ev, 1);
-  ra.fail = e->d_fail.p;
-  ra.prof = nullptr;
-  ra.skip = dead_skip(e, env, group_reps(plan, g)) ? 1 : 0;
   if (profile) {
     const size_t words = (size_t)Rg * K * ksim_replay::kProfPhases;
     if ((rc = e->d_prof.ensure(words))) return rc;
@@ -3902,7 +3747,7 @@ static int launch_group_reports(ksim_engine* e, const RunPlan& plan, int ovl_gro
 
 // The persistent path: plan, upload the order, fork, launch each group, reports, join.
 static int run_persistent(ksim_engine* e, const RunEnv& env, int max_ev) {
-  const RunPlan plan = make_run_plan(e, env);
+  const RunPlan plan = make_run_plan(run_plan_input(e, env));
   int rc = upload_go_states(e, plan);
   if (rc) return rc;
   e->last_memo = e->last_hmemo = e->last_rgo = e->last_scan1 = 0;
@@ -4187,6 +4032,41 @@ int ksim_engine_set_shard_peers(ksim_engine* e, const uint8_t* handles) {
   return KSIM_OK;
 }
 
+// ---- the steps the node-sharded runs share ----
+// One shard back to its initial state, enqueued on `st`: the node records and tag counts, the report's last-event
+// table when the report is on (the k_step path only: no replay kernel of a shard reports), and with `results` the
+// result records (the replay kernels write a result only where a shard has one to report).
+static int reset_shard_state(ksim_engine* e, hipStream_t st, bool results) {
+  KSIM_HIP(hipMemcpyAsync(e->d_nodes.p, e->d_nodes_init.p, sizeof(NodeRec) * (size_t)e->N, hipMemcpyDeviceToDevice, st));
+  KSIM_HIP(hipMemcpyAsync(e->d_tags.p, e->d_tags_init.p, sizeof(uint16_t) * e->tags_stride, hipMemcpyDeviceToDevice, st));
+  if (results)
+    KSIM_HIP(hipMemsetAsync(e->d_res[0].p, 0xff, sizeof(ResultDev) * (size_t)std::max(e->n_events[0], 1), st));
+  if (e->report) KSIM_HIP(hipMemsetAsync(e->d_last.p, 0xff, sizeof(int32_t) * (size_t)e->N, st));
+  return KSIM_OK;
+}
+
+// The end of an in-process group's run on engine 0's stream: the closing event, the wait, the fail word of the
+// group's one launch, then the run's time and diagnostics on every engine.  K = 0: the per-pod k_step path, which
+// has no fail word and no width.
+static int finish_group_run(ksim_engine* const* engines, int world, int max_ev, int K, const char* kernel, bool hmemo) {
+  ksim_engine* e0 = engines[0];
+  KSIM_HIP(hipEventRecord(e0->ev1, e0->stream));
+  KSIM_HIP(hipStreamSynchronize(e0->stream));
+  int fail = 0;
+  if (K > 0) KSIM_HIP(hipMemcpy(&fail, e0->d_fail.p, sizeof(int), hipMemcpyDeviceToHost));
+  if (fail) return KSIM_ESTATE;
+  float ms = 0;
+  KSIM_HIP(hipEventElapsedTime(&ms, e0->ev0, e0->ev1));
+  for (int k = 0; k < world; ++k) {
+    engines[k]->last_ms = ms;
+    engines[k]->last_steps = max_ev;
+    if (K > 0) engines[k]->last_K = K;
+    if (hmemo) engines[k]->last_hmemo = 1;
+    engines[k]->last_kernels = kernel;
+  }
+  return KSIM_OK;
+}
+
 // ksim_engine_run of a shard with peers: k_hmemo over this shard's slices, the exchange spanning every
 // shard's workgroups (K per shard, the same K and S on every rank: from n_global and world only).
 static int run_hmemo_peer(ksim_engine* e, const RunEnv& env, int max_ev) {
@@ -4194,11 +4074,9 @@ static int run_hmemo_peer(ksim_engine* e, const RunEnv& env, int max_ev) {
   if (e->R != 1 || e->reps[0].policy != POL_FGD || e->report || go_random(e, 0) || !score_table())
     return KSIM_ENOTSUP;
   const int world = e->shard_world;
-  const int nmax = (e->n_global + world - 1) / world;
-  const HSlices sl = hmemo_slices(nmax, std::max(1, 64 / world), kClampKeepK);
-  const int K = sl.K, S = sl.S;
-  const int Kt = world * K;
-  if (Kt > 256 || e->N > K * S) return KSIM_ENOTSUP;
+  const ShardSlices sl = hmemo_peer_slices(e->n_global, world, e->N);
+  if (!sl.ok) return KSIM_ENOTSUP;
+  const int K = sl.K, S = sl.S, Kt = world * K;
   const int stride = std::max(max_ev, 1);
   hipStream_t st = e->stream;
   const int zero = 0;
@@ -4207,9 +4085,7 @@ static int run_hmemo_peer(ksim_engine* e, const RunEnv& env, int max_ev) {
   if (rc) return rc;
   if (!e->hmemo.ok) return KSIM_ENOTSUP;
   e->mplan_dirty = true;
-  KSIM_HIP(hipMemcpyAsync(e->d_nodes.p, e->d_nodes_init.p, sizeof(NodeRec) * (size_t)e->N, hipMemcpyDeviceToDevice, st));
-  KSIM_HIP(hipMemcpyAsync(e->d_tags.p, e->d_tags_init.p, sizeof(uint16_t) * e->tags_stride, hipMemcpyDeviceToDevice, st));
-  KSIM_HIP(hipMemsetAsync(e->d_res[0].p, 0xff, sizeof(ResultDev) * (size_t)stride, st));
+  if ((rc = reset_shard_state(e, st, true))) return rc;
   if ((rc = hmemo_init_keys(e, 1, 0, st, e->node_off))) return rc;
   HMemoArgs a = hmemo_args(e, env, 0, stride);
   a.roff = e->node_off;
@@ -4289,18 +4165,11 @@ static int run_replay_group(ksim_engine* const* engines, int world, const RunEnv
   int N = 1;  // slices cover the largest shard
   for (int k = 0; k < world; ++k) N = std::max(N, engines[k]->N);
   const int pol = e0->reps[0].policy;
-  // slices of about 384 nodes (choose_wgs), at most 256 columns in all
-  int K = std::max(1, std::min(256 / world, (N + 383) / 384));
-  K = std::min(K, std::max(1, e0->cus / world));
-  int S = (N + K - 1) / K;
-  while (replay_lds(S, pol, false) > 160 * 1024 && (K + 1) * world <= std::min(256, e0->cus)) {
-    ++K;
-    S = (N + K - 1) / K;
-  }
-  const int Kt = world * K;
-  if (Kt < 2 || replay_lds(S, pol, false) > 160 * 1024) return KSIM_OK;
+  const ShardSlices sl = replay_group_slices(N, world, e0->cus, pol);
+  if (!sl.ok) return KSIM_OK;
+  const int K = sl.K, S = sl.S, Kt = world * K;
   const void* f = replay_kernel(pol, Kt, false);
-  const size_t lds = replay_lds(S, pol, false);
+  const size_t lds = replay::replay_lds(S, pol, false);
   if (Kt > resident_cap(e0, f, lds)) return KSIM_OK;
   hipStream_t st = e0->stream;
   KSIM_HIP(hipSetDevice(e0->device));
@@ -4317,46 +4186,18 @@ static int run_replay_group(ksim_engine* const* engines, int world, const RunEnv
   for (int k = 0; k < world; ++k) {
     ksim_engine* e = engines[k];
     KSIM_HIP(hipStreamSynchronize(e->stream));
-    KSIM_HIP(hipMemcpyAsync(e->d_nodes.p, e->d_nodes_init.p, sizeof(NodeRec) * (size_t)e->N, hipMemcpyDeviceToDevice, st));
-    KSIM_HIP(hipMemcpyAsync(e->d_tags.p, e->d_tags_init.p, sizeof(uint16_t) * e->tags_stride, hipMemcpyDeviceToDevice, st));
-    KSIM_HIP(hipMemsetAsync(e->d_res[0].p, 0xff, sizeof(ResultDev) * (size_t)std::max(e->n_events[0], 1), st));
+    if ((rc = reset_shard_state(e, st, true))) return rc;
     KSIM_HIP(hipMemcpyAsync(e0->d_rgreps.p + k, e->d_reps.p, sizeof(ReplicaDev), hipMemcpyDeviceToDevice, st));
     skip = skip && dead_skip(e, env, std::vector<int>{0});
   }
-  ReplayArgs ra;
-  std::memset(&ra, 0, sizeof ra);
-  ra.reps = e0->d_rgreps.p;
-  ra.rep_list = e0->d_rglist.p;
-  ra.N = N;
-  ra.K = K;
-  ra.S = S;
-  ra.gran = e0->d_rgran.p;
-  ra.hist = nullptr;
-  ra.hist_stride = std::max(max_ev, 1);
-  ra.fail = e0->d_fail.p;
-  ra.prof = nullptr;
-  ra.skip = skip ? 1 : 0;
-  ra.pf_guess = 1;
-  ra.xK = Kt;
-  ra.group = 1;
+  ReplayArgs ra =
+      replay_args(e0->d_rgreps.p, e0->d_rglist.p, N, K, S, e0->d_rgran.p, nullptr, max_ev, e0->d_fail.p, skip, Kt);
   KSIM_HIP(hipMemsetAsync(e0->d_rgran.p, 0, sizeof(unsigned long long) * 2 * (size_t)Kt * kGranW, st));
   KSIM_HIP(hipMemsetAsync(e0->d_fail.p, 0, sizeof(int), st));
   KSIM_HIP(hipEventRecord(e0->ev0, st));
   const TypDev* tp = e0->d_tp.p;  // (the cheap policies read no typical table)
   if ((rc = launch_persistent(f, Kt, kRBlock, lds, st, e0->coop, ra, tp))) return rc;
-  KSIM_HIP(hipEventRecord(e0->ev1, st));
-  KSIM_HIP(hipStreamSynchronize(st));
-  int fail = 0;
-  KSIM_HIP(hipMemcpy(&fail, e0->d_fail.p, sizeof(int), hipMemcpyDeviceToHost));
-  if (fail) return KSIM_ESTATE;
-  float ms = 0;
-  KSIM_HIP(hipEventElapsedTime(&ms, e0->ev0, e0->ev1));
-  for (int k = 0; k < world; ++k) {
-    engines[k]->last_ms = ms;
-    engines[k]->last_steps = max_ev;
-    engines[k]->last_K = K;
-    engines[k]->last_kernels = "k_replay_group";
-  }
+  if ((rc = finish_group_run(engines, world, max_ev, K, "k_replay_group", false))) return rc;
   *done = true;
   return KSIM_OK;
 }
@@ -4369,10 +4210,9 @@ static int run_hmemo_group(ksim_engine* const* engines, int world, const RunEnv&
   const int stride = std::max(max_ev, 1);
   int nmax = 1;
   for (int k = 0; k < world; ++k) nmax = std::max(nmax, engines[k]->N);
-  const HSlices sl = hmemo_slices(nmax, std::max(1, std::min(64, e0->cus / world)), kClamp);
-  const int K = sl.K, S = sl.S;
-  const int Kt = world * K;
-  if (K < 1 || Kt > 256 || K * S < nmax) return KSIM_OK;
+  const ShardSlices sl = hmemo_group_slices(nmax, world, e0->cus);
+  if (!sl.ok) return KSIM_OK;
+  const int K = sl.K, S = sl.S, Kt = world * K;
   std::vector<HMemoArgs> args(world);
   size_t lds = 0;
   for (int k = 0; k < world; ++k) {
@@ -4395,9 +4235,7 @@ static int run_hmemo_group(ksim_engine* const* engines, int world, const RunEnv&
   for (int k = 0; k < world; ++k) {
     ksim_engine* e = engines[k];
     KSIM_HIP(hipStreamSynchronize(e->stream));
-    KSIM_HIP(hipMemcpyAsync(e->d_nodes.p, e->d_nodes_init.p, sizeof(NodeRec) * (size_t)e->N, hipMemcpyDeviceToDevice, st));
-    KSIM_HIP(hipMemcpyAsync(e->d_tags.p, e->d_tags_init.p, sizeof(uint16_t) * e->tags_stride, hipMemcpyDeviceToDevice, st));
-    KSIM_HIP(hipMemsetAsync(e->d_res[0].p, 0xff, sizeof(ResultDev) * (size_t)std::max(e->n_events[0], 1), st));
+    if ((rc = reset_shard_state(e, st, true))) return rc;
     rc = hmemo_init_keys(e, 1, 0, st, e->node_off);
     if (rc) return rc;
     HMemoArgs a = hmemo_args(e, env, 0, stride);
@@ -4429,19 +4267,7 @@ static int run_hmemo_group(ksim_engine* const* engines, int world, const RunEnv&
     return KSIM_OK;
   }
   KSIM_HIP(lr);
-  KSIM_HIP(hipEventRecord(e0->ev1, st));
-  KSIM_HIP(hipStreamSynchronize(st));
-  int fail = 0;
-  KSIM_HIP(hipMemcpy(&fail, e0->d_fail.p, sizeof(int), hipMemcpyDeviceToHost));
-  if (fail) return KSIM_ESTATE;
-  float ms = 0;
-  KSIM_HIP(hipEventElapsedTime(&ms, e0->ev0, e0->ev1));
-  for (int k = 0; k < world; ++k) {
-    engines[k]->last_ms = ms;
-    engines[k]->last_steps = max_ev;
-    engines[k]->last_K = K;
-    engines[k]->last_hmemo = 1;
-  }
+  if ((rc = finish_group_run(engines, world, max_ev, K, "k_hmemo_group", true))) return rc;
   *done = true;
   return KSIM_OK;
 }
@@ -4463,8 +4289,6 @@ int ksim_shard_group_run(ksim_engine* const* engines, int world) {
   if (hmemo_group_eligible(engines, world, env)) {
     bool done = false;
     const int rc = run_hmemo_group(engines, world, env, max_ev, &done);
-    if (!rc && done)
-      for (int k = 0; k < world; ++k) engines[k]->last_kernels = "k_hmemo_group";
     if (rc || done) return rc;
   }
   if (replay_group_eligible(engines, world, env)) {
@@ -4472,7 +4296,7 @@ int ksim_shard_group_run(ksim_engine* const* engines, int world) {
     const int rc = run_replay_group(engines, world, env, max_ev, &done);
     if (rc || done) return rc;
   }
-  for (int k = 0; k < world; ++k) engines[k]->last_kernels = "k_step";
+  for (int k = 0; k < world; ++k) engines[k]->last_kernels = "k_step";  // (named first: a failed run names its path too)
   if (int rc = e0->d_ptrs.ensure(32)) return rc;
   std::vector<unsigned long long*> ptrs(32, nullptr);
   for (int k = 0; k < world; ++k) {
@@ -4481,15 +4305,12 @@ int ksim_shard_group_run(ksim_engine* const* engines, int world) {
   }
   hipStream_t st = e0->stream;
   KSIM_HIP(hipMemcpyAsync(e0->d_ptrs.p, ptrs.data(), sizeof(unsigned long long*) * 32, hipMemcpyHostToDevice, st));
+  int rc;
   for (int k = 0; k < world; ++k) {
-    ksim_engine* e = engines[k];
-    KSIM_HIP(hipStreamSynchronize(e->stream));
-    KSIM_HIP(hipMemcpyAsync(e->d_nodes.p, e->d_nodes_init.p, sizeof(NodeRec) * (size_t)e->N, hipMemcpyDeviceToDevice, st));
-    KSIM_HIP(hipMemcpyAsync(e->d_tags.p, e->d_tags_init.p, sizeof(uint16_t) * e->tags_stride, hipMemcpyDeviceToDevice, st));
-    if (e->report) KSIM_HIP(hipMemsetAsync(e->d_last.p, 0xff, sizeof(int32_t) * (size_t)e->N, st));
+    KSIM_HIP(hipStreamSynchronize(engines[k]->stream));
+    if ((rc = reset_shard_state(engines[k], st, false))) return rc;
   }
   KSIM_HIP(hipEventRecord(e0->ev0, st));
-  int rc;
   for (int s = 0; s < max_ev; ++s) {
     for (int k = 0; k < world; ++k)
       if ((rc = shard_local(engines[k], st, nullptr, s))) return rc;
@@ -4501,15 +4322,7 @@ int ksim_shard_group_run(ksim_engine* const* engines, int world) {
   }
   for (int k = 0; k < world; ++k)
     if (engines[k]->report && (rc = run_report(engines[k], max_ev, engines[k]->stream, nullptr, engines[k]->R))) return rc;
-  KSIM_HIP(hipEventRecord(e0->ev1, st));
-  KSIM_HIP(hipStreamSynchronize(st));
-  float ms = 0;
-  KSIM_HIP(hipEventElapsedTime(&ms, e0->ev0, e0->ev1));
-  for (int k = 0; k < world; ++k) {
-    engines[k]->last_ms = ms;
-    engines[k]->last_steps = max_ev;
-  }
-  return KSIM_OK;
+  return finish_group_run(engines, world, max_ev, 0, "k_step", false);
 }
 
 int ksim_engine_set_report(ksim_engine* e, int enable) {

@@ -1,11 +1,14 @@
-// ksim_plan.hpp -- host-side planning of the memoised FGD replays (k_memo, ksim_memo.hpp; k_hmemo, ksim_hmemo.hpp).
+// ksim_plan.hpp -- host-side planning: the memoised FGD replays (k_memo, ksim_memo.hpp; k_hmemo, ksim_hmemo.hpp), the
+// run plan of the persistent path (make_run_plan: which kernel every replica runs on, in which order, on which stream,
+// at what width) and the slices of the node-sharded runs.
 //
 // Everything here is arithmetic over vectors: which workgroup owns which pod class, how wide a launch is, how its LDS
 // is carved, which instantiation of a kernel a run takes.  No HIP call and no environment read: the engine
-// (ksim_engine.hip) fills a PlanInput from its own state, the knobs it read (RunEnv) and a residency query bound to the
-// kernel, so the same code runs in a CPU-only test (tests/native_host/plan_check.cpp).  The two LDS layouts are
-// KSIM_HD: k_hmemo carves its dynamic LDS with the function the planner sizes it with; k_memo's carving is written out
-// at the top of the kernel (its register allocation is sensitive to it) and held to memo_layout by that test.
+// (ksim_engine.hip) fills a PlanInput / RunPlanInput from its own state, the knobs it read (RunEnv) and a residency
+// query bound to the kernel, so the same code runs in a CPU-only test (tests/native_host/plan_check.cpp).  The LDS
+// layouts are host-and-device functions: k_hmemo, k_replay and k_scan1 carve their dynamic LDS with the function the
+// planner sizes it with; k_memo's carving is written out at the top of the kernel (its register allocation is
+// sensitive to it) and held to memo_layout by that test.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -24,6 +27,12 @@ namespace ksim_plan {
 using namespace ksim;
 
 constexpr size_t kLdsMax = 160 * 1024;  // LDS of one CU (gfx950)
+
+// Slices of a node-sharded launch: K workgroups per shard, S nodes (k_hmemo: ranks) each; !ok: the group does not fit.
+struct ShardSlices {
+  int K, S;
+  bool ok;
+};
 
 // ---- k_memo: limits and LDS layout (ksim_memo.hpp takes them from here) ----
 namespace memo {
@@ -115,7 +124,77 @@ inline HSlices hmemo_slices(int n, int want, SliceClamp clamp) {
   if (cut) S = kMaxNb * kFan;
   return {S, clamp == kClampKeepK && !cut ? want : (n + S - 1) / S};
 }
+// One shard per process (ksim_engine_run of a shard with peers): the same K and S on every rank, from n_global and
+// world only; refused when the exchange would pass 256 columns or this shard's N nodes pass its slices.
+inline ShardSlices hmemo_peer_slices(int n_global, int world, int N) {
+  const HSlices sl = hmemo_slices((n_global + world - 1) / world, std::max(1, 64 / world), kClampKeepK);
+  return {sl.K, sl.S, world * sl.K <= 256 && N <= sl.K * sl.S};
+}
+// The in-process shard group over shards of at most nmax nodes.
+inline ShardSlices hmemo_group_slices(int nmax, int world, int cus) {
+  const HSlices sl = hmemo_slices(nmax, std::max(1, std::min(64, cus / world)), kClamp);
+  return {sl.K, sl.S, sl.K >= 1 && world * sl.K <= 256 && sl.K * sl.S >= nmax};
+}
 }  // namespace hmemo
+
+// ---- k_replay: limits and LDS layout (ksim_replay.hpp takes them from here) ----
+namespace replay {
+constexpr int kMaxK = 256;     // workgroups per replica (<= 64: one granule column per polling lane)
+constexpr int kPfGuess = 256;  // PWR+FGD: entries of the guessed-range table (class id mod 256)
+constexpr int kTagStride = 16;  // u16 tag counts per node
+// sizeof(ReplayShared), sizeof(ReplayFgd): the structs stay beside the kernel, which asserts both
+constexpr size_t kSharedBytes = 5248, kFgdBytes = 20864;
+
+// The dynamic LDS layout of one k_replay workgroup (host and device).
+struct RLayout {
+  size_t fgd, nodes, tags, F0, E0, pe, last, praw, pinf, gtab, pver, pm, total;
+};
+// pm_c > 0 (PWR+FGD): u32 pver[S+1] (each slot's state version) and uint2 pm[pm_c][S] (every class's
+// memoised Filter + Score of every real slot, valid while its version matches; pf_memo_* in ksim_replay.hpp)
+__host__ __device__ inline RLayout replay_layout(int S, int pol, bool general, int pm_c = 0) {
+  const bool tags = pol == POL_CLUSTERING, fgd = pol == POL_FGD || pol == POL_PWR_FGD;
+  const bool pwr = pol == POL_PWR || pol == POL_PWR_FGD, pf = pol == POL_PWR_FGD;
+  const size_t S1 = (size_t)S + 1;
+  RLayout L;
+  size_t o = kSharedBytes;
+  L.fgd = o;   o += fgd ? kFgdBytes : 0;
+  L.nodes = o; o += S1 * sizeof(NodeRec);
+  L.tags = o;  o += tags ? S1 * kTagStride * sizeof(uint16_t) : 0;
+  L.F0 = o;    o += fgd ? S1 * sizeof(double) : 0;
+  L.E0 = o;    o += pwr ? S1 * sizeof(double) : 0;
+  L.pe = o;    o += pwr ? S1 * sizeof(int2) : 0;
+  L.last = o;  o += general ? S1 * sizeof(int) : 0;
+  L.praw = o;  o += pf ? 2 * S1 * sizeof(int) : 0;  // by step parity: the pending step's stays intact
+  L.pinf = o;  o += pf ? 2 * S1 * sizeof(int) : 0;
+  o = (o + 15) / 16 * 16;
+  L.gtab = o;  o += pf ? kPfGuess * sizeof(int4) : 0;
+  L.pver = o;  o += (pf && pm_c > 0) ? (S1 * sizeof(unsigned) + 15) / 16 * 16 : 0;
+  L.pm = o;    o += (pf && pm_c > 0) ? (size_t)pm_c * S * sizeof(uint2) : 0;
+  L.total = o;
+  return L;
+}
+inline size_t replay_lds(int S, int pol, bool general) {  // S real slots + the virtual node
+  return replay_layout(S, pol, general).total;
+}
+}  // namespace replay
+
+// ---- k_scan1: limits and LDS size (ksim_scan1.hpp takes them from here) ----
+namespace scan1 {
+constexpr int kBlock = 256;
+constexpr int kRegSlots = 5;  // kReg: node slots per thread held in VGPRs (N <= 1280, the openb clusters)
+constexpr int kPolMix = 65;   // scan1_lds's policy id of a k_scan1_mix launch (the presence bits always present)
+constexpr size_t kSharedBytes = 4864;  // sizeof(Scan1Shared): the struct stays beside the kernel, which asserts it
+// k_scan1 has an instantiation for these policies (the engine's scan1_fn names them; launch_scan1 refuses a null)
+inline bool scan1_serves(int pol) { return pol >= POL_BESTFIT && pol <= POL_RANDOM; }
+
+// Dynamic LDS: Scan1Shared | NodeRec nodes[N] (not with kReg) | u16 tag presence[N] rounded up to 16 B
+// (GpuClustering, and every k_scan1_mix launch) | i32 last[N] (report)
+__host__ __device__ inline size_t scan1_tm_bytes(int N) { return ((size_t)N * sizeof(uint16_t) + 15) & ~(size_t)15; }
+__host__ __device__ inline size_t scan1_lds(int N, int pol, bool report, bool reg = false) {
+  return kSharedBytes + (reg ? 0 : (size_t)N * sizeof(NodeRec)) +
+         (pol == POL_CLUSTERING || pol == kPolMix ? scan1_tm_bytes(N) : 0) + (report ? (size_t)N * 4 : 0);
+}
+}  // namespace scan1
 
 // ---- which instantiation a launch takes ----
 // The engine maps a form's code() to a function pointer in one switch over the enumerators below (no default: a form
@@ -606,6 +685,245 @@ inline bool hmemo_plan(const PlanInput& in, int stride, HPlan& pl, int forceK = 
     std::copy(sof[i].begin(), sof[i].end(), pl.nstate.begin() + (size_t)i * pl.Npad);
   }
   return true;
+}
+
+// ---- the run plan: everything a persistent run decides, before it launches anything ----
+// Which kernel every replica runs on, in which order, on which stream, at what width.  The engine fills a RunPlanInput
+// (run_plan_input) once prepare_memo has made the FGD plans, and launches what the plan says.
+struct RunReplica {
+  int policy = 0;
+  bool go_random = false;  // Random on Go's math/rand stream (k_random_go)
+  int n_events = 0;
+  bool has_delete = false;
+  int dpcfg = 0;  // DotProduct: dimExtMethod | normMethod << 4
+};
+struct RunPlanInput {
+  std::vector<RunReplica> reps;
+  int N = 0, cus = 0, wgs_req = 0, run_mode = 0;
+  bool report = false;
+  int scan1 = 0;  // 0: no k_scan1, 1: the node records in LDS, 2: in VGPRs where they fit
+  // the FGD plans of the run (prepare_memo): split: the wide-hinted replicas on k_memo, the others on k_hmemo
+  bool split_fgd = false, memo_ok = false, hmemo_ok = false;
+  int memo_nwg = 0, hmemo_K = 1;            // k_memo's workgroups in all, k_hmemo's per replica
+  std::vector<int> memo_reps, hmemo_reps;   // the replicas of each plan, in its order
+  // the run's knobs (RunEnv)
+  bool timers = false, scan1_mix = true;
+  int side_streams = 4;
+};
+
+// Group kinds of a run beside the policies themselves (and scan1::kPolMix)
+constexpr int kPolRandomGo = 64;  // the k_random_go replicas
+constexpr int kPolFgdH = 66;      // the one-workgroup FGD replicas on k_hmemo beside wide ones on k_memo (split_fgd)
+
+enum GroupKernel { kRunRandomGo, kRunScan1, kRunMemo, kRunHmemo, kRunReplay, kRunNone };
+
+struct PlanGroup {
+  int kind = 0;              // a policy, kPolFgdH, scan1::kPolMix or kPolRandomGo
+  int first = 0, count = 0;  // its replicas: RunPlan::order[first .. first + count)
+  GroupKernel kernel = kRunReplay;  // (kRunNone: an FGD group the required memoised kernel has no plan for)
+  int side = -1;             // its side stream's index; -1: the engine stream
+  int K = 1, S = 0;          // k_replay and k_scan1 groups: workgroups per replica, nodes per slice, dynamic LDS bytes
+  size_t lds = 0;            // (k_replay: a co-resident grid the device cannot hold is narrowed at launch)
+};
+
+struct RunPlan {
+  std::vector<int> order;  // the replicas in launch order (uploaded as d_replist)
+  std::vector<PlanGroup> groups;
+  bool any_delete = false, general = false;  // general: k_replay's instantiation with timers, report stores, deletes
+  bool concurrent = false;                   // the groups on side streams, else back to back on the engine stream
+  bool reg1 = false;                         // k_scan1 keeps the node records in VGPRs
+  int fgd_cus = 0;                           // CUs the FGD groups hold (a k_memo / k_hmemo workgroup fills a CU's registers)
+};
+
+// Workgroups per replica for k_replay: every workgroup of a launch must be
+// co-resident (they exchange granules every step), so R*K never exceeds one
+// workgroup per CU; K = 1 needs no co-residency at all.
+inline int choose_wgs(int cus, int N, int wgs_req, int R) {
+  // auto: one workgroup per CU up to 64 per replica; large clusters (C5: 100k nodes) go wider
+  // so that a slice stays near 384 nodes (one to two FGD evaluation rounds per step)
+  int K = wgs_req;
+  if (K <= 0) {
+    K = std::min(cus / R, 64);
+    K = std::max(K, std::min(cus / R, (N + 383) / 384));
+  }
+  K = std::max(1, std::min(K, replay::kMaxK));
+  K = std::min(K, N);
+  if (R * K > cus) K = 1;
+  return K;
+}
+
+// K, S and LDS bytes of a k_replay group: choose_wgs, then narrower slices until the layout fits in LDS (or cannot
+// be narrowed further: the launcher refuses a layout that still does not fit).  Returns choose_wgs' own K.
+inline int replay_fit(const RunPlanInput& in, bool general, PlanGroup& g) {
+  const int K0 = g.K = choose_wgs(in.cus, in.N, in.wgs_req, g.count);
+  g.S = (in.N + g.K - 1) / g.K;
+  while (replay::replay_lds(g.S, g.kind, general) > kLdsMax && g.K < replay::kMaxK && g.count * (g.K + 1) <= in.cus) {
+    ++g.K;
+    g.S = (in.N + g.K - 1) / g.K;
+  }
+  g.lds = replay::replay_lds(g.S, g.kind, general);
+  return K0;
+}
+
+// The launcher's narrowing of a K > 1 k_replay grid against `cap`, the workgroups the occupancy query says can be
+// resident at once: fewer, larger slices when it is short.  lds: the layout's bytes at a slice size.
+enum NarrowRefusal { kNarrowOk, kNarrowAsked, kNarrowLds };  // kNarrowAsked: the run's own width holds no replica each
+struct ReplayNarrow {
+  int K, S;
+  NarrowRefusal refused;
+};
+inline ReplayNarrow replay_narrow(int K, int cap, int Rg, int N, int wgs_req, const std::function<size_t(int S)>& lds) {
+  const int S = (N + K - 1) / K;
+  if (Rg * K <= cap) return {K, S, kNarrowOk};
+  if (wgs_req > 0 && cap < Rg) return {K, S, kNarrowAsked};
+  const int K2 = std::max(1, std::min(K, cap / Rg)), S2 = (N + K2 - 1) / K2;
+  return {K2, S2, lds(S2) > kLdsMax ? kNarrowLds : kNarrowOk};
+}
+
+// Slices of the in-process k_replay shard group (lean cheap policies) over shards of at most nmax nodes: about 384
+// nodes each (choose_wgs), at most 256 columns over the world, widened until the layout fits in LDS; not ok when the
+// layout does not fit or the exchange would have a single column.
+inline ShardSlices replay_group_slices(int nmax, int world, int cus, int pol) {
+  int K = std::max(1, std::min(256 / world, (nmax + 383) / 384));
+  K = std::min(K, std::max(1, cus / world));
+  int S = (nmax + K - 1) / K;
+  while (replay::replay_lds(S, pol, false) > kLdsMax && (K + 1) * world <= std::min(256, cus)) {
+    ++K;
+    S = (nmax + K - 1) / K;
+  }
+  return {K, S, world * K >= 2 && replay::replay_lds(S, pol, false) <= kLdsMax};
+}
+
+// The replicas ordered into groups: a split FGD run's two plans first, then one group per policy present, the
+// Random replicas on Go's stream last (one k_random_go workgroup each).
+inline void plan_order(const RunPlanInput& in, RunPlan& pl) {
+  const int R = (int)in.reps.size();
+  auto add = [&](int kind, int count) {
+    PlanGroup g;
+    g.kind = kind;
+    g.count = count;
+    if (count) pl.groups.push_back(g);
+  };
+  if (in.split_fgd) {  // the wide FGD replicas (k_memo) first, then the one-workgroup ones (k_hmemo): the plans' orders
+    pl.order = in.memo_reps;
+    pl.order.insert(pl.order.end(), in.hmemo_reps.begin(), in.hmemo_reps.end());
+    add(POL_FGD, (int)in.memo_reps.size());
+    add(kPolFgdH, (int)in.hmemo_reps.size());
+  }
+  for (int pol = in.split_fgd ? POL_BESTFIT : POL_FGD; pol <= POL_PWR_FGD; ++pol) {
+    int c = 0;
+    for (int r = 0; r < R; ++r)
+      if (in.reps[r].policy == pol && !in.reps[r].go_random) { pl.order.push_back(r); ++c; }
+    add(pol, c);
+  }
+  int c = 0;
+  for (int r = 0; r < R; ++r)
+    if (in.reps[r].go_random) { pl.order.push_back(r); ++c; }
+  add(kPolRandomGo, c);
+}
+
+// Each group's kernel (with the k_replay fit of those that have no other), and whether the groups run concurrently on
+// side streams: when every group is at ONE workgroup per replica (no cross-workgroup exchange, so no co-residency
+// needed; a paper-sweep group fills 170 of 256 CUs, the next group's workgroups take the rest).  A group needing K > 1,
+// a k_memo launch outside a split FGD run or the profile timers keep the launches back to back on the engine stream.
+inline void plan_kernels(const RunPlanInput& in, RunPlan& pl) {
+  pl.concurrent = !in.timers && pl.groups.size() >= 2;
+  for (PlanGroup& g : pl.groups) {
+    const bool fgd = g.kind == POL_FGD && in.run_mode != 2;
+    if (g.kind == kPolRandomGo) {  // one workgroup per replica
+      g.kernel = kRunRandomGo;
+    } else if (fgd && in.memo_ok) {  // (a split FGD run's wide group is launched first, behind its gate)
+      g.kernel = kRunMemo;
+      pl.concurrent = pl.concurrent && in.split_fgd;
+    } else if ((fgd || g.kind == kPolFgdH) && in.hmemo_ok) {  // concurrent at one workgroup per replica
+      g.kernel = kRunHmemo;
+      pl.concurrent = pl.concurrent && (g.kind == kPolFgdH || in.hmemo_K == 1);
+    } else {
+      const int K0 = replay_fit(in, pl.general, g);
+      if (g.kind != kPolFgdH) pl.concurrent = pl.concurrent && g.K == 1;
+      // one workgroup per replica, create-only, a cheap policy: the 256-thread k_scan1 (ksim_scan1.hpp)
+      const bool one = K0 == 1 && !in.timers && !pl.any_delete && in.scan1 && in.N <= kMaxSlice &&
+                       scan1::scan1_serves(g.kind) && scan1::scan1_lds(in.N, g.kind, in.report, pl.reg1) <= kLdsMax;
+      if ((fgd || g.kind == kPolFgdH) && in.run_mode >= 3 && in.run_mode <= 5) {
+        g.kernel = kRunNone;
+      } else if (one) {
+        g.kernel = kRunScan1;
+        g.K = 1;
+        g.S = in.N;
+        g.lds = scan1::scan1_lds(in.N, g.kind, in.report, pl.reg1);
+      }
+    }
+  }
+}
+
+// The cheap-policy groups a concurrent run would give one k_scan1 launch each become ONE k_scan1_mix launch (policy
+// per workgroup), its replicas longest stream first, where the first of them stood: the run then needs one side
+// stream beside the FGD group's, whatever the hardware-queue mapping of the process.
+inline void plan_mix(const RunPlanInput& in, RunPlan& pl) {
+  if (!(pl.concurrent && !pl.any_delete && in.scan1 && in.N <= kMaxSlice && in.scan1_mix &&
+        scan1::scan1_lds(in.N, scan1::kPolMix, in.report, pl.reg1) <= kLdsMax))
+    return;
+  std::vector<int> mix, norder;
+  std::vector<PlanGroup> ngroups;
+  int f = 0, at = -1, nmix = 0;
+  for (const PlanGroup& g : pl.groups) {
+    bool m = g.kind >= POL_BESTFIT && g.kind <= POL_RANDOM;
+    for (int j = f; m && j < f + g.count; ++j)
+      m = g.kind != POL_DOTPROD || in.reps[pl.order[j]].dpcfg == (DIM_MERGE | NORM_MAX << 4);
+    if (m) {
+      mix.insert(mix.end(), pl.order.begin() + f, pl.order.begin() + f + g.count);
+      if (at < 0) at = (int)ngroups.size();
+      ++nmix;
+    } else {
+      ngroups.push_back(g);
+      norder.insert(norder.end(), pl.order.begin() + f, pl.order.begin() + f + g.count);
+    }
+    f += g.count;
+  }
+  if (nmix < 2) return;
+  std::stable_sort(mix.begin(), mix.end(), [&](int x, int y) { return in.reps[x].n_events > in.reps[y].n_events; });
+  int off = 0;
+  for (int g = 0; g < at; ++g) off += ngroups[g].count;
+  norder.insert(norder.begin() + off, mix.begin(), mix.end());
+  PlanGroup mg;
+  mg.kind = scan1::kPolMix;
+  mg.count = (int)mix.size();
+  mg.kernel = kRunScan1;
+  mg.K = 1;
+  mg.S = in.N;
+  mg.lds = scan1::scan1_lds(in.N, scan1::kPolMix, in.report, pl.reg1);
+  ngroups.insert(ngroups.begin() + at, mg);
+  pl.order.swap(norder);
+  pl.groups.swap(ngroups);
+}
+
+// What a run launches, in which order, on which streams.
+inline RunPlan make_run_plan(const RunPlanInput& in) {
+  RunPlan pl;
+  for (const RunReplica& r : in.reps) pl.any_delete = pl.any_delete || r.has_delete;
+  pl.general = in.timers || in.report || pl.any_delete;
+  pl.reg1 = in.scan1 == 2 && in.N <= scan1::kBlock * scan1::kRegSlots;
+  plan_order(in, pl);
+  plan_kernels(in, pl);
+  plan_mix(in, pl);
+  // The side streams share the process's hardware queues (GPU_MAX_HW_QUEUES, HIP's default 4), and two streams on one
+  // queue run their kernels one after the other.  So no more side streams than queues (side_streams): the first
+  // group (FGD on k_hmemo, the longest in a paper sweep) gets one to itself, the others take the rest round robin.  A
+  // split FGD run's wide k_memo group runs on the engine stream itself, which otherwise only waits: three groups then
+  // need two side streams (with three, two groups shared a queue: 64 -> 133 ms for a C4 share, profiles/r06/c4_wide/).
+  const int nq = in.side_streams, g_off = in.split_fgd ? 1 : 0;
+  int first = 0;
+  for (int gi = 0; gi < (int)pl.groups.size(); ++gi) {
+    PlanGroup& g = pl.groups[gi];
+    g.first = first;
+    first += g.count;
+    const int j = gi - g_off;
+    g.side = !pl.concurrent || j < 0 ? -1 : (j == 0 || nq == 1) ? 0 : 1 + (j - 1) % (nq - 1);
+    if (g.kind == kPolFgdH) pl.fgd_cus += g.count;
+    else if (g.kind == POL_FGD && in.run_mode != 2)
+      pl.fgd_cus += in.memo_ok ? in.memo_nwg : g.count * (in.hmemo_ok ? in.hmemo_K : 1);
+  }
+  return pl;
 }
 
 }  // namespace ksim_plan

@@ -38,16 +38,19 @@
 namespace ksim_replay {
 
 using namespace ksim;
+// kMaxK, kPfGuess and the LDS layout: ksim_plan.hpp (the host's run planner sizes launches with them)
+using ksim_plan::replay::kMaxK;
+using ksim_plan::replay::kPfGuess;
+using ksim_plan::replay::RLayout;
+using ksim_plan::replay::replay_layout;
 
 constexpr int kRBlock = 1024;
 constexpr int kRWaves = kRBlock / 64;
 constexpr int kChunk = kRBlock;      // nodes per chunk, one lane per node (non-FGD policies)
 constexpr int kFChunk = kRBlock / 8; // nodes per chunk, 8 lanes per node -- lane g <-> GPU g (FGD)
 constexpr int kRMaxCand = 9;         // FGD items per node: stale current state + up to 8 candidates
-constexpr int kMaxK = 256;         // workgroups per replica (<= 64: one granule column per polling lane)
 constexpr int kGran = 3;           // granules per workgroup per step (the key exchange)
 constexpr int kGranW = 10;         // granule words per workgroup per parity: key round 0-2; PWR+FGD's round 0-6, its miss round 7-8
-constexpr int kPfGuess = 256;      // PWR+FGD: entries of the guessed-range table (class id mod 256)
 constexpr unsigned kSpinLimit = 1u << 22;  // ~seconds: only a non-resident workgroup can stall a poll
 constexpr int kEvBuf = 128;        // events staged in LDS per refill (4 KB)
 
@@ -111,6 +114,8 @@ struct __align__(16) ReplayShared {
   unsigned dead[32];            // classes with no feasible node (create-only streams: for good)
 };
 static_assert(sizeof(ReplayShared) % 16 == 0, "keep the node records 16-B aligned");
+static_assert(sizeof(ReplayShared) == ksim_plan::replay::kSharedBytes,
+              "replay_layout (ksim_plan.hpp) starts the regions after ReplayShared");
 
 // FGD evaluation scratch (FGD, PWR+FGD launches only).
 struct __align__(16) ReplayFgd {
@@ -121,35 +126,8 @@ struct __align__(16) ReplayFgd {
   uint8_t pad_[(16 - (kFChunk * kRMaxCand * 3) % 16) % 16];
 };
 static_assert(sizeof(ReplayFgd) % 16 == 0, "keep the node records 16-B aligned");
-
-// The dynamic LDS layout of one k_replay workgroup (host and device).
-struct RLayout {
-  size_t fgd, nodes, tags, F0, E0, pe, last, praw, pinf, gtab, pver, pm, total;
-};
-// pm_c > 0 (PWR+FGD): u32 pver[S+1] (each slot's state version) and uint2 pm[pm_c][S] (every class's
-// memoised Filter + Score of every real slot, valid while its version matches; pf_memo_* below)
-__host__ __device__ inline RLayout replay_layout(int S, int pol, bool general, int pm_c = 0) {
-  const bool tags = pol == POL_CLUSTERING, fgd = pol == POL_FGD || pol == POL_PWR_FGD;
-  const bool pwr = pol == POL_PWR || pol == POL_PWR_FGD, pf = pol == POL_PWR_FGD;
-  const size_t S1 = (size_t)S + 1;
-  RLayout L;
-  size_t o = sizeof(ReplayShared);
-  L.fgd = o;   o += fgd ? sizeof(ReplayFgd) : 0;
-  L.nodes = o; o += S1 * sizeof(NodeRec);
-  L.tags = o;  o += tags ? S1 * kTagStride * sizeof(uint16_t) : 0;
-  L.F0 = o;    o += fgd ? S1 * sizeof(double) : 0;
-  L.E0 = o;    o += pwr ? S1 * sizeof(double) : 0;
-  L.pe = o;    o += pwr ? S1 * sizeof(int2) : 0;
-  L.last = o;  o += general ? S1 * sizeof(int) : 0;
-  L.praw = o;  o += pf ? 2 * S1 * sizeof(int) : 0;  // by step parity: the pending step's stays intact
-  L.pinf = o;  o += pf ? 2 * S1 * sizeof(int) : 0;
-  o = (o + 15) / 16 * 16;
-  L.gtab = o;  o += pf ? kPfGuess * sizeof(int4) : 0;
-  L.pver = o;  o += (pf && pm_c > 0) ? (S1 * sizeof(unsigned) + 15) / 16 * 16 : 0;
-  L.pm = o;    o += (pf && pm_c > 0) ? (size_t)pm_c * S * sizeof(uint2) : 0;
-  L.total = o;
-  return L;
-}
+static_assert(sizeof(ReplayFgd) == ksim_plan::replay::kFgdBytes,
+              "replay_layout (ksim_plan.hpp) sizes the FGD scratch");
 
 // PWR+FGD memo entry of one (class, slot): x = the raw PWR score, y = the packed FGD score / GPU choices
 // (pinf's low 16 bits), Filter's verdict (16), the Score error (17) and the slot version it was computed

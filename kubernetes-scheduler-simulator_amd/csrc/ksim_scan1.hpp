@@ -31,10 +31,14 @@ namespace ksim_scan1 {
 
 using namespace ksim;
 
-constexpr int kBlock = 256;
+// kBlock, kRegSlots, kPolMix and the LDS size: ksim_plan.hpp (the host's run planner reads them)
+using ksim_plan::scan1::kBlock;
+using ksim_plan::scan1::kRegSlots;
+using ksim_plan::scan1::kPolMix;
+using ksim_plan::scan1::scan1_tm_bytes;
+using ksim_plan::scan1::scan1_lds;
 constexpr int kWaves = kBlock / 64;
 constexpr int kEvBuf = 128;
-constexpr int kRegSlots = 5;  // kReg: node slots per thread held in VGPRs (N <= 1280, the openb clusters)
 
 struct Scan1Args {
   ReplicaDev* reps;
@@ -64,15 +68,8 @@ struct __align__(16) Scan1Shared {
   unsigned dead[kWaves][kDeadWords];  // each wave's copy of the dead classes (every wave decides alike)
 };
 static_assert(sizeof(Scan1Shared) % 16 == 0, "keep the node records 16-B aligned");
-
-// Dynamic LDS: Scan1Shared | NodeRec nodes[N] (not with kReg) | u16 tag presence[N] rounded up to 16 B
-// (GpuClustering, and every k_scan1_mix launch) | i32 last[N] (report)
-constexpr int kPolMix = 65;  // scan1_lds's policy id of a k_scan1_mix launch (the presence bits always present)
-__host__ __device__ inline size_t scan1_tm_bytes(int N) { return ((size_t)N * sizeof(uint16_t) + 15) & ~(size_t)15; }
-__host__ __device__ inline size_t scan1_lds(int N, int pol, bool report, bool reg = false) {
-  return sizeof(Scan1Shared) + (reg ? 0 : (size_t)N * sizeof(NodeRec)) +
-         (pol == POL_CLUSTERING || pol == kPolMix ? scan1_tm_bytes(N) : 0) + (report ? (size_t)N * 4 : 0);
-}
+static_assert(sizeof(Scan1Shared) == ksim_plan::scan1::kSharedBytes,
+              "scan1_lds (ksim_plan.hpp) starts the node records after Scan1Shared");
 
 // x = c ? y : x field by field (a select of whole structs would take the array's address)
 __device__ __forceinline__ void sel_node(NodeV& x, const NodeV& y, bool c) {

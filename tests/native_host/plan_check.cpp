@@ -2,14 +2,17 @@
 // over seeded random inputs, the plans of the bench's C2 job and C5's slices against the values the engine printed on
 // the GPU (profiles/r08/memo/parent_memo_prof.log, profiles/r04/hmemo/prof_rm5_gkey.log, profiles/r05/hmemo/), the
 // slice geometry against the formulas the three call sites had, and memo_form / hmemo_form over every input against
-// the nested conditionals they replaced.  Host code only: no device, no HIP call.  Aborts on the first broken
-// expectation; prints one tally line per group, then "ok".
+// the nested conditionals they replaced.  The run plan (make_run_plan): the nine cases of tests/test_gpu_run_plan.py
+// as inputs with their plans written out, invariants over seeded random inputs, and choose_wgs / replay_fit /
+// replay_narrow / the node-sharded runs' slices against the formulas the engine had.  Host code only: no device, no
+// HIP call.  Aborts on the first broken expectation; prints one tally line per group, then "ok".
 //
 // usage: plan_check <node csv> <pod csv>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
 #include <set>
+#include <string>
 #include <tuple>
 
 #include "ksim_plan.hpp"
@@ -592,6 +595,361 @@ void check_forms() {
   std::printf("forms: memo_inputs=%d memo_forms=%zu hmemo_inputs=%d hmemo_forms=%zu\n", nm, mcodes.size(), nh, hcodes.size());
 }
 
+// ---- the run plan (make_run_plan) ----
+// What the last_run_* getters would show of a plan: the kernel names (each once, in launch order), the launches, the
+// side streams used.
+struct Seen {
+  std::vector<std::string> kernels;
+  int launches, streams;
+};
+Seen seen_of(const RunPlanInput& in, const RunPlan& pl) {
+  Seen s{{}, (int)pl.groups.size(), 0};
+  std::set<int> sides;
+  for (const PlanGroup& g : pl.groups) {
+    const char* nm = g.kernel == kRunRandomGo ? "k_random_go"
+                     : g.kernel == kRunScan1  ? (g.kind == scan1::kPolMix ? "k_scan1_mix" : "k_scan1")
+                     : g.kernel == kRunMemo   ? "k_memo"
+                     : g.kernel == kRunHmemo  ? (in.hmemo_K == 1 ? "k_hmemo" : "k_hmemo_wide")
+                     : g.kernel == kRunReplay ? "k_replay" : "none";
+    if (std::find(s.kernels.begin(), s.kernels.end(), nm) == s.kernels.end()) s.kernels.push_back(nm);
+    if (g.side >= 0) sides.insert(g.side);
+  }
+  s.streams = (int)sides.size();
+  return s;
+}
+
+struct WantGroup {
+  int kind, count;
+  GroupKernel kernel;
+  int side, K;
+};
+RunReplica rr(int policy, int n_events = 300, bool go = false, bool del = false) { return {policy, go, n_events, del, 0}; }
+
+// The nine cases of tests/test_gpu_run_plan.py (the openb default cluster: 1213 nodes, 256 CUs, wgs_per_replica = 1
+// unless the case says otherwise, four hardware queues) as planner inputs, with the plans written out.  The FGD plans
+// are what prepare_memo makes there: at one workgroup per replica k_memo has no plan and k_hmemo has one at K = 1.
+void check_run_plan_cases() {
+  const int mix = scan1::kPolMix;
+  auto base = [](std::vector<RunReplica> reps) {
+    RunPlanInput in;
+    in.reps = std::move(reps);
+    in.N = 1213;
+    in.cus = 256;
+    in.wgs_req = 1;
+    in.scan1 = 2;
+    in.side_streams = 4;
+    return in;
+  };
+  auto hmemo1 = [](RunPlanInput in, std::vector<int> reps) {
+    in.hmemo_ok = true;
+    in.hmemo_K = 1;
+    in.hmemo_reps = std::move(reps);
+    return in;
+  };
+  struct Case {
+    const char* name;
+    RunPlanInput in;
+    std::vector<int> order;
+    std::vector<WantGroup> groups;
+    Seen want;  // the `want` tuple of the GPU test: kernels, launches, side streams
+    bool concurrent;
+  };
+  std::vector<Case> cases;
+  const std::vector<RunReplica> sweep = {rr(POL_FGD), rr(POL_FGD, 260), rr(POL_BESTFIT, 280), rr(POL_PACKING)};
+  cases.push_back({"a-fgd-beside-mix", hmemo1(base(sweep), {0, 1}), {0, 1, 3, 2},
+                   {{POL_FGD, 2, kRunHmemo, 0, 1}, {mix, 2, kRunScan1, 1, 1}}, {{"k_hmemo", "k_scan1_mix"}, 2, 2}, true});
+  {
+    RunPlanInput in = hmemo1(base(sweep), {0, 1});
+    in.report = true;
+    cases.push_back({"b-overlapped-report", in, {0, 1, 3, 2},
+                     {{POL_FGD, 2, kRunHmemo, 0, 1}, {mix, 2, kRunScan1, 1, 1}}, {{"k_hmemo", "k_scan1_mix"}, 2, 2}, true});
+  }
+  {
+    RunPlanInput in = base({rr(POL_FGD), rr(POL_BESTFIT)});
+    in.wgs_req = 0;
+    in.memo_ok = true;  // k_memo at K = 64
+    in.memo_nwg = 64;
+    in.memo_reps = {0};
+    cases.push_back({"c-memo-back-to-back", in, {0, 1},
+                     {{POL_FGD, 1, kRunMemo, -1, 1}, {POL_BESTFIT, 1, kRunReplay, -1, 64}}, {{"k_memo", "k_replay"}, 2, 0}, false});
+  }
+  {
+    RunPlanInput in = hmemo1(base(sweep), {1});  // replica 0 hinted to six workgroups: the split
+    in.split_fgd = in.memo_ok = true;
+    in.memo_nwg = 6;
+    in.memo_reps = {0};
+    cases.push_back({"d-split-fgd", in, {0, 1, 3, 2},
+                     {{POL_FGD, 1, kRunMemo, -1, 1}, {kPolFgdH, 1, kRunHmemo, 0, 1}, {mix, 2, kRunScan1, 1, 1}},
+                     {{"k_memo", "k_hmemo", "k_scan1_mix"}, 3, 2}, true});
+  }
+  cases.push_back({"e-deletes-general-replay", base({rr(POL_PACKING, 299, false, true), rr(POL_BESTFIT)}), {1, 0},
+                   {{POL_BESTFIT, 1, kRunReplay, 0, 1}, {POL_PACKING, 1, kRunReplay, 1, 1}}, {{"k_replay"}, 2, 2}, true});
+  cases.push_back({"f-random-go-last", base({rr(POL_RANDOM, 300, true), rr(POL_BESTFIT, 280), rr(POL_PACKING)}), {2, 1, 0},
+                   {{mix, 2, kRunScan1, 0, 1}, {kPolRandomGo, 1, kRunRandomGo, 1, 1}}, {{"k_scan1_mix", "k_random_go"}, 2, 2},
+                   true});
+  for (int nq : {1, 2}) {
+    RunPlanInput in = base({rr(POL_BESTFIT), rr(POL_DOTPROD, 260), rr(POL_PACKING, 280), rr(POL_CLUSTERING, 240), rr(POL_RANDOM)});
+    in.scan1_mix = false;
+    in.side_streams = nq;
+    const int s = nq - 1;  // every group after the first on the last side stream
+    cases.push_back({nq == 1 ? "g-round-robin-1" : "g-round-robin-2", in, {0, 1, 2, 3, 4},
+                     {{POL_BESTFIT, 1, kRunScan1, 0, 1}, {POL_DOTPROD, 1, kRunScan1, s, 1}, {POL_PACKING, 1, kRunScan1, s, 1},
+                      {POL_CLUSTERING, 1, kRunScan1, s, 1}, {POL_RANDOM, 1, kRunScan1, s, 1}},
+                     {{"k_scan1"}, 5, nq}, true});
+  }
+  {
+    RunPlanInput in = base({rr(POL_PWR_FGD)});
+    in.run_mode = 2;
+    cases.push_back({"h-pwr-fgd-replay", in, {0}, {{POL_PWR_FGD, 1, kRunReplay, -1, 1}}, {{"k_replay"}, 1, 0}, false});
+  }
+  CHECK(cases.size() == 9);
+  for (const Case& c : cases) {
+    const RunPlan pl = make_run_plan(c.in);
+    if (pl.order != c.order || pl.groups.size() != c.groups.size() || pl.concurrent != c.concurrent) {
+      std::fprintf(stderr, "plan_check: run plan case %s\n", c.name);
+      CHECK(!"the plan's order, group count or concurrency differs");
+    }
+    int first = 0;
+    for (size_t i = 0; i < c.groups.size(); ++i) {
+      const PlanGroup& g = pl.groups[i];
+      const WantGroup& w = c.groups[i];
+      if (g.kind != w.kind || g.count != w.count || g.kernel != w.kernel || g.side != w.side || g.K != w.K || g.first != first) {
+        std::fprintf(stderr, "plan_check: run plan case %s group %zu\n", c.name, i);
+        CHECK(!"the group differs");
+      }
+      first += g.count;
+    }
+    const Seen s = seen_of(c.in, pl);
+    CHECK(s.kernels == c.want.kernels && s.launches == c.want.launches && s.streams == c.want.streams);
+  }
+  // what the launchers read beside the groups
+  const RunPlan a = make_run_plan(cases[0].in), b = make_run_plan(cases[1].in), c = make_run_plan(cases[2].in),
+                d = make_run_plan(cases[3].in), e = make_run_plan(cases[4].in);
+  CHECK(a.reg1 && !a.general && a.fgd_cus == 2 && a.groups[1].lds == 7296 && a.groups[1].S == 1213);
+  CHECK(b.general && b.groups[1].lds == 7296 + 4 * 1213);  // the report's last-event table
+  CHECK(c.fgd_cus == 64 && c.groups[1].S == 19 && c.groups[1].lds == replay::replay_lds(19, POL_BESTFIT, false));
+  CHECK(d.fgd_cus == 7);
+  CHECK(e.any_delete && e.general && e.groups[0].lds == replay::replay_lds(1213, POL_BESTFIT, true));
+}
+
+// The formulas the planner's arithmetic had in the engine, restated.
+int old_choose_wgs(int cus, int N, int wgs_req, int R) {
+  int K = wgs_req;
+  if (K <= 0) {
+    K = std::min(cus / R, 64);
+    K = std::max(K, std::min(cus / R, (N + 383) / 384));
+  }
+  K = std::max(1, std::min(K, 256));
+  K = std::min(K, N);
+  if (R * K > cus) K = 1;
+  return K;
+}
+size_t old_replay_lds(int S, int pol, bool general) { return replay::replay_layout(S, pol, general).total; }
+
+long check_run_formulas() {
+  long n = 0;
+  static const int Ns[] = {1, 2, 63, 384, 385, 1213, 4095, 4096, 5000, 24576, 100000};
+  static const int wgs[] = {0, 1, 7, 64, 300};
+  for (int cus : {64, 256, 304})
+    for (int R = 1; R <= 40; ++R)
+      for (int N : Ns)
+        for (int wr : wgs) {
+          const int K0 = old_choose_wgs(cus, N, wr, R);
+          CHECK(choose_wgs(cus, N, wr, R) == K0);
+          ++n;
+          for (int pol = POL_FGD; pol <= POL_PWR_FGD; ++pol)
+            for (bool general : {false, true}) {
+              // replay_fit as it stood
+              int K = K0, S = (N + K - 1) / K;
+              while (old_replay_lds(S, pol, general) > 160 * 1024 && K < 256 && R * (K + 1) <= cus) {
+                ++K;
+                S = (N + K - 1) / K;
+              }
+              RunPlanInput in;
+              in.N = N;
+              in.cus = cus;
+              in.wgs_req = wr;
+              PlanGroup g;
+              g.kind = pol;
+              g.count = R;
+              CHECK(replay_fit(in, general, g) == K0 && g.K == K && g.S == S && g.lds == old_replay_lds(S, pol, general));
+              ++n;
+              if (K == 1 || g.lds > 160 * 1024) continue;  // (the launcher queries no occupancy, or has refused)
+              // launch_replay's narrowing as it stood, at the residencies around the grid's size
+              for (int cap : {0, 1, R - 1, R, R * K / 2, R * K - 1, R * K, 2 * cus}) {
+                int K2 = K, S2 = S, rc = 0;  // rc 1: the silent refusal, 2: the one with the message
+                if (R * K2 > cap) {
+                  if (wr > 0 && cap < R) rc = 1;
+                  else {
+                    K2 = std::max(1, std::min(K2, cap / R));
+                    S2 = (N + K2 - 1) / K2;
+                    if (old_replay_lds(S2, pol, general) > 160 * 1024) rc = 2;
+                  }
+                }
+                const ReplayNarrow nw = replay_narrow(K, cap, R, N, wr, [&](int s) { return old_replay_lds(s, pol, general); });
+                CHECK(nw.refused == (rc == 0 ? kNarrowOk : rc == 1 ? kNarrowAsked : kNarrowLds));
+                if (rc != 1) CHECK(nw.K == K2 && nw.S == S2);
+                ++n;
+              }
+            }
+        }
+  return n;
+}
+
+// Invariants of make_run_plan over seeded random inputs.
+void fuzz_run_plan(int cases) {
+  std::set<int> kernels;
+  int conc = 0, b2b = 0, split = 0, mixed = 0;
+  for (int n = 0; n < cases; ++n) {
+    Rng g(9000 + n);
+    RunPlanInput in;
+    const int R = pick(g, 1, 40);
+    const bool cheap = pick(g, 0, 2) == 0;  // the paper sweep's shape: few FGD replicas among cheap ones
+    std::vector<int> fgd;
+    for (int r = 0; r < R; ++r) {
+      RunReplica v;
+      v.policy = cheap && pick(g, 0, 5) ? pick(g, POL_BESTFIT, POL_RANDOM) : pick(g, POL_FGD, POL_PWR_FGD);
+      v.go_random = v.policy == POL_RANDOM && pick(g, 0, 2) == 0;
+      v.n_events = pick(g, 0, 400);
+      v.has_delete = pick(g, 0, 40) == 0;
+      v.dpcfg = pick(g, 0, 3) ? (DIM_MERGE | NORM_MAX << 4) : (pick(g, 0, 3) | pick(g, 0, 2) << 4);
+      if (v.policy == POL_FGD) fgd.push_back(r);
+      in.reps.push_back(v);
+    }
+    in.N = pick(g, 0, 1) ? pick(g, 1, 1300) : pick(g, 1, 5000);
+    static const int cus[] = {64, 256, 304}, wgs[] = {0, 1, 7, 64};
+    in.cus = cus[pick(g, 0, 2)];
+    in.wgs_req = wgs[pick(g, 0, 3)];
+    in.run_mode = pick(g, 0, 2) ? 0 : pick(g, 0, 5);
+    in.report = pick(g, 0, 1) == 1;
+    in.scan1 = pick(g, 0, 2);
+    in.timers = pick(g, 0, 9) == 0;
+    in.scan1_mix = pick(g, 0, 4) != 0;
+    in.side_streams = pick(g, 1, 6);
+    // the FGD plans as prepare_memo leaves them: none, k_memo for all, k_hmemo for all, or (run_mode 0) the split
+    const int how = fgd.empty() || in.run_mode == 1 || in.run_mode == 2 ? 0 : pick(g, 0, in.run_mode == 0 && fgd.size() >= 2 ? 3 : 2);
+    if (how == 1) {
+      in.memo_ok = true;
+      in.memo_reps = fgd;
+      in.memo_nwg = pick(g, (int)fgd.size(), std::max((int)fgd.size(), in.cus));
+    } else if (how == 2) {
+      in.hmemo_ok = true;
+      in.hmemo_reps = fgd;
+      in.hmemo_K = pick(g, 0, 2) ? 1 : pick(g, 2, 64);
+    } else if (how == 3) {
+      in.split_fgd = in.memo_ok = in.hmemo_ok = true;
+      const int nw = pick(g, 1, (int)fgd.size() - 1);
+      in.memo_reps.assign(fgd.begin(), fgd.begin() + nw);
+      in.hmemo_reps.assign(fgd.begin() + nw, fgd.end());
+      in.memo_nwg = 2 * nw;
+      in.hmemo_K = 1;
+    }
+    const RunPlan pl = make_run_plan(in);
+    // order: a permutation, tiled by the groups
+    std::vector<int> sorted = pl.order;
+    std::sort(sorted.begin(), sorted.end());
+    for (int r = 0; r < R; ++r) CHECK((int)sorted.size() == R && sorted[r] == r);
+    int first = 0, nmix = 0;
+    bool all_engine = true, any_delete = false;
+    for (const RunReplica& v : in.reps) any_delete = any_delete || v.has_delete;
+    CHECK(pl.any_delete == any_delete && pl.general == (in.timers || in.report || any_delete));
+    for (size_t gi = 0; gi < pl.groups.size(); ++gi) {
+      const PlanGroup& q = pl.groups[gi];
+      CHECK(q.first == first && q.count > 0);
+      first += q.count;
+      std::set<int> pols;
+      for (int j = q.first; j < q.first + q.count; ++j) {
+        const RunReplica& v = in.reps[pl.order[j]];
+        pols.insert(v.policy);
+        if (q.kind == kPolRandomGo) CHECK(v.go_random);
+        else if (q.kind == kPolFgdH) CHECK(v.policy == POL_FGD && in.split_fgd);
+        else if (q.kind == scan1::kPolMix)
+          CHECK(!v.go_random && v.policy >= POL_BESTFIT && v.policy <= POL_RANDOM &&
+                (v.policy != POL_DOTPROD || v.dpcfg == (DIM_MERGE | NORM_MAX << 4)));
+        else CHECK(v.policy == q.kind && !v.go_random);
+        // the mixed launch: longest stream first
+        if (q.kind == scan1::kPolMix && j > q.first) CHECK(in.reps[pl.order[j - 1]].n_events >= v.n_events);
+      }
+      if (q.kind == kPolRandomGo) CHECK(gi + 1 == pl.groups.size() && q.kernel == kRunRandomGo);  // Go's stream last
+      else CHECK(q.kernel != kRunRandomGo);
+      if (q.kind == scan1::kPolMix) {
+        ++nmix;
+        CHECK(pols.size() >= 2 && q.kernel == kRunScan1 && pl.concurrent && in.scan1_mix);
+      }
+      CHECK(q.side >= -1 && q.side < in.side_streams);
+      all_engine = all_engine && q.side == -1;
+      if (!pl.concurrent) CHECK(q.side == -1);
+      if (q.kernel == kRunScan1 || q.kernel == kRunReplay) {
+        CHECK(q.K >= 1 && (long)q.K * q.S >= in.N);
+        if (pl.concurrent) CHECK(q.K == 1);
+        CHECK(q.count * q.K <= in.cus || q.K == 1);
+      }
+      if (q.kernel == kRunScan1) {
+        CHECK(!any_delete && !in.timers && in.scan1 && in.N <= kMaxSlice && q.K == 1 && q.S == in.N && q.lds <= kLdsMax);
+        CHECK(q.lds == scan1::scan1_lds(in.N, q.kind, in.report, pl.reg1) && (q.kind == scan1::kPolMix || scan1::scan1_serves(q.kind)));
+      }
+      if (q.kernel == kRunReplay) CHECK(q.lds == replay::replay_lds(q.S, q.kind, pl.general));
+      if (q.kernel == kRunMemo) CHECK(q.kind == POL_FGD && in.memo_ok && (!pl.concurrent || in.split_fgd));
+      if (q.kernel == kRunHmemo) CHECK((q.kind == POL_FGD || q.kind == kPolFgdH) && in.hmemo_ok && (!pl.concurrent || in.hmemo_K == 1));
+      if (q.kernel == kRunNone) CHECK(q.kind == POL_FGD && in.run_mode >= 3 && in.run_mode <= 5);
+      kernels.insert((int)q.kernel);
+    }
+    CHECK(first == R && nmix <= 1);
+    CHECK(all_engine == !pl.concurrent);
+    CHECK(pl.reg1 == (in.scan1 == 2 && in.N <= 1280));
+    if (in.timers || pl.groups.size() < 2) CHECK(!pl.concurrent || nmix == 1);
+    conc += pl.concurrent;
+    b2b += !pl.concurrent;
+    split += in.split_fgd && pl.concurrent;
+    mixed += nmix;
+  }
+  CHECK(kernels.size() == 6 && conc > 0 && b2b > 0 && split > 0 && mixed > 0);
+  check_run_plan_cases();
+  const long formulas = check_run_formulas();
+  std::printf("run_plan: cases=9 fuzz=%d concurrent=%d back_to_back=%d split=%d mix=%d kernels=%zu formulas=%ld\n", cases, conc,
+              b2b, split, mixed, kernels.size(), formulas);
+}
+
+// ---- the node-sharded runs' slices against what their call sites computed ----
+void check_shard_slices() {
+  long n = 0;
+  for (int world = 1; world <= 16; ++world)
+    for (int nmax = 64; nmax <= 200000; ++nmax) {
+      for (int cus : {8, 256, 304}) {
+        for (int pol : {(int)POL_BESTFIT, (int)POL_CLUSTERING}) {  // (the cheap policies' layouts differ in the tags only)
+          // run_replay_group: slices of about 384 nodes, at most 256 columns in all, widened until the layout fits
+          int K = std::max(1, std::min(256 / world, (nmax + 383) / 384));
+          K = std::min(K, std::max(1, cus / world));
+          int S = (nmax + K - 1) / K;
+          while (old_replay_lds(S, pol, false) > 160 * 1024 && (K + 1) * world <= std::min(256, cus)) {
+            ++K;
+            S = (nmax + K - 1) / K;
+          }
+          const bool fits = !(world * K < 2 || old_replay_lds(S, pol, false) > 160 * 1024);
+          const ShardSlices sl = replay_group_slices(nmax, world, cus, pol);
+          CHECK(sl.K == K && sl.S == S && sl.ok == fits);
+          ++n;
+        }
+        {  // run_hmemo_group
+          const hmemo::HSlices h = hmemo::hmemo_slices(nmax, std::max(1, std::min(64, cus / world)), hmemo::kClamp);
+          const ShardSlices sl = hmemo::hmemo_group_slices(nmax, world, cus);
+          CHECK(sl.K == h.K && sl.S == h.S && sl.ok == !(h.K < 1 || world * h.K > 256 || h.K * h.S < nmax));
+          ++n;
+        }
+      }
+      // run_hmemo_peer: the shard sizes a cluster of about world x nmax nodes is cut into
+      for (int n_global : {world * nmax, world * nmax - world + 1})
+        for (int N : {nmax, nmax - 1, nmax + 4096}) {
+          const int nm = (n_global + world - 1) / world;
+          const hmemo::HSlices h = hmemo::hmemo_slices(nm, std::max(1, 64 / world), hmemo::kClampKeepK);
+          const ShardSlices sl = hmemo::hmemo_peer_slices(n_global, world, N);
+          CHECK(sl.K == h.K && sl.S == h.S && sl.ok == !(world * h.K > 256 || N > h.K * h.S));
+          ++n;
+        }
+    }
+  std::printf("shard_slices: compared=%ld\n", n);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -604,6 +962,8 @@ int main(int argc, char** argv) {
   check_recorded(argv[1], argv[2]);
   check_slices();
   check_forms();
+  fuzz_run_plan(3000);
+  check_shard_slices();
   std::printf("ok\n");
   return 0;
 }

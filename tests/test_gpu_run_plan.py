@@ -6,7 +6,9 @@ orders its replicas longest stream first) at wgs_per_replica=1 unless the case s
 tuples are literals, observed on the engine as it stood before its run path was split into a plan and
 per-kernel launchers; the side-stream counts follow GPU_MAX_HW_QUEUES (no more side streams than hardware
 queues).  Each replica's decisions and final state are also compared with the oracle, so a wrong replica
-order or rep_list offset shows up as well.
+order or rep_list offset shows up as well.  The plan itself is host-only code (make_run_plan, ksim_plan.hpp):
+tests/native_host/plan_check.cpp holds these nine cases as planner inputs with their plans written out, and
+must be kept in step with CASES.
 """
 import os
 
