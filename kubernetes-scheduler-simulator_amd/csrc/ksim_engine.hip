@@ -2259,10 +2259,18 @@ static int print_memo_trace(ksim_engine* e, const MemoPlan& pl, DevBuf<unsigned 
   auto at = [&](int w, int s, int k) { return (double)h[((size_t)w * TS + s) * kT + k]; };
   double crit = 0, hand = 0, hmax = 0, period = 0, lag = 0, f0 = 0, spin = 0, nhand = 0;
   int nc = 0, nh = 0, nf = 0, nn = 0;
+  // the steps whose granule left before the critical F (d cannot host the step's class), [1], against the others, [0]
+  double ecrit[2] = {0, 0}, ehand[2] = {0, 0};
+  int enc[2] = {0, 0}, enn[2] = {0, 0}, nearly = 0;
+  for (int s = 0; s < TS; ++s)  // every traced step, the first and the last included
+    if (evo[s] >= 0 && at(evo[s] >> 16, s, 3) > at(evo[s] >> 16, s, 1)) ++nearly;
   for (int s = 1; s + 1 < TS; ++s) {
     if (evo[s] < 0 || evo[s + 1] < 0) continue;
     const int o = evo[s] >> 16, o2 = evo[s + 1] >> 16;
     crit += at(o, s, 1) - at(o, s, 0);
+    const int ee = at(o, s, 3) > at(o, s, 1) ? 1 : 0;  // the F join came after the publish
+    ecrit[ee] += at(o, s, 1) - at(o, s, 0);
+    ++enc[ee];
     if (at(o, s, 2) > 0 && at(o, s, 3) > 0) {
       f0 += at(o, s, 3) - at(o, s, 0);   // start -> all critical F done
       spin += at(o, s, 2) - at(o, s, 3); // -> fresh key known
@@ -2273,6 +2281,8 @@ static int print_memo_trace(ksim_engine* e, const MemoPlan& pl, DevBuf<unsigned 
     if (o2 != o) {  // the hand-off the chain goes through: the next owner's own receive, not the mean of all
       nhand += at(o2, s, 1) - at(o, s, 1);
       ++nn;
+      ehand[ee] += at(o2, s, 1) - at(o, s, 1);
+      ++enn[ee];
     }
     ++nc;
     for (int w = 0; w < K; ++w) {
@@ -2289,6 +2299,11 @@ static int print_memo_trace(ksim_engine* e, const MemoPlan& pl, DevBuf<unsigned 
                  "next owner publish->receive %.3f (%d of %d steps hand over)\n",
                  TS, crit / nc / 100, hand / nh / 100, hmax / 100, lag / nc / 100, period / nc / 100,
                  nf ? f0 / nf / 100 : 0.0, nf ? (f0 + spin) / nf / 100 : 0.0, nn ? nhand / nn / 100 : 0.0, nn, nc);
+  if (nc && nh)
+    std::fprintf(stderr, "ksim memo trace, early publish (d cannot host the step's class): %d of the %d traced steps; owner "
+                 "start->publish early %.3f (%d), other %.3f (%d); next owner publish->receive early %.3f (%d), other %.3f (%d)\n",
+                 nearly, TS, enc[1] ? ecrit[1] / enc[1] / 100 : 0.0, enc[1], enc[0] ? ecrit[0] / enc[0] / 100 : 0.0, enc[0],
+                 enn[1] ? ehand[1] / enn[1] / 100 : 0.0, enn[1], enn[0] ? ehand[0] / enn[0] / 100 : 0.0, enn[0]);
   return KSIM_OK;
 }
 

@@ -1098,29 +1098,54 @@ __global__ __launch_bounds__(kMBlock) void k_memo(MemoArgs a, const TypDev* __re
         if (lane == 0) { sh.wtop[wv][0] = a1; sh.wtop[wv][1] = a2; }
       }
     }
-    // ---- the owner publishes the step's winner (wave 0, as soon as waves 1-9 have their F).
-    // Everything that does not depend on this step's F values -- the precomputed best of the other
-    // nodes (ex) and Reserve's GPU choice on it, the class requests, d's feasibility and old key --
-    // is loaded while waves 1-9 evaluate F; after the wait only d's key, the max and the granule store
-    // remain before the winner is out.
+    // ---- the owner publishes the step's winner (wave 0).  W = max(ex, fresh): ex is the precomputed best of the
+    // other nodes, fresh = d's new key for the step's own class, 0 when Filter refuses d.  When d cannot host the
+    // class (or no node changed) the winner is ex whatever waves 1-9 return, so the granule leaves at once (`early`)
+    // and the wait for their F, the score group's keys on d and the result row follow it, off the step chain.
+    // Otherwise everything that does not depend on this step's F values -- Reserve's GPU choice on ex and on d,
+    // the class requests, d's old key -- is loaded while waves 1-9 evaluate F; after the wait only d's key, the
+    // max and the granule store remain before the winner is out.
     unsigned gk_crit = 0u;
     if (own && wv == 0) {
+      // first what the early case needs: ex, Filter of the own class on d, Reserve on ex
       const unsigned t2a = sh.t2a, t2b = sh.t2b;
       const unsigned ex = (d >= 0 && t2a != 0u && key32_rank(t2a) == d) ? t2b : t2a;
-      const int cnt_o = sh.cnt[oslot];
-      unsigned old_own = 0u, fresh = 0u;
-      bool ofeas = false;
-      PodDev cp{};
-      if (d >= 0) {
-        old_own = s_keys[(size_t)oslot * N + d];
-        cp = ksim_replay::uniform_pod(&sh.cls[crep]);
-        ofeas = filter_node(dn, ksim_replay::uniform_pod(&sh.cls[oslot]));
-      }
+      const bool ofeas = d >= 0 && filter_node(dn, ksim_replay::uniform_pod(&sh.cls[oslot]));
       const int mask_ex =
           ex != 0u ? select_gpus(load_node(&s_nodes[key32_rank(ex)]), p, rp.gpusel, key32_gpu(ex), rp.seed, step) : -1;
       // Reserve on d: only the FGD / PWR selectors of a share pod depend on the key's GPU
       const bool d_gpu_from_key = is_share_pod(p) && p.milli > 0 && (rp.gpusel == SEL_FGD || rp.gpusel == SEL_PWR);
-      const int mask_d_pre = d >= 0 && !d_gpu_from_key ? select_gpus(dn, p, rp.gpusel, -1, rp.seed, step) : -1;
+      const bool early = d < 0 || !ofeas;
+      int mask_d_pre = -1;
+      unsigned W = 0u, pay = 0u;
+      int rk = -1, mask = -1;
+      auto publish = [&](unsigned fresh) {
+        W = fresh > ex ? fresh : ex;
+        rk = W != 0u ? key32_rank(W) : -1;
+        // Reserve (open_gpu_share.go:178-205) on the winner: d's record is in registers
+        const int gW = key32_gpu(W);
+        mask = W == 0u ? -1 : (W == ex ? mask_ex : (d_gpu_from_key ? (gW < 0 ? -1 : 1 << gW) : mask_d_pre));
+        // bit 1: no feasible node at all (W == 0), as opposed to a Reserve failure on the winner
+        pay = (W != 0u && mask >= 0) ? pack_pay(rk, mask) : (W == 0u ? 3u : 1u);
+        if (lane == 0) {
+          gstore32(win + step, pay);
+          asm volatile("" ::: "memory");
+          sh.pay = pay;
+          if (prof) sh.prof[20] += __builtin_amdgcn_s_memrealtime() - t_loaded;
+          if (trace && step < a.trace_steps)
+            trace[((size_t)blockIdx.x * a.trace_steps + step) * kTrace + 1] = __builtin_amdgcn_s_memrealtime();
+        }
+      };
+      if (early) publish(0u);
+      // needed only behind the early store
+      const int cnt_o = sh.cnt[oslot];
+      unsigned old_own = 0u, fresh = 0u;
+      PodDev cp{};
+      if (d >= 0) {
+        old_own = s_keys[(size_t)oslot * N + d];
+        cp = ksim_replay::uniform_pod(&sh.cls[crep]);
+        if (ofeas && !d_gpu_from_key) mask_d_pre = select_gpus(dn, p, rp.gpusel, -1, rp.seed, step);
+      }
       if (prof && tid == 0) sh.prof[16] += __builtin_amdgcn_s_memrealtime() - t_loaded;
       if (d >= 0) {
         if (lane == 0) {  // wait for waves 1-9 (LDS counter; every one of them arrives after its own F, nothing
@@ -1141,7 +1166,7 @@ __global__ __launch_bounds__(kMBlock) void k_memo(MemoArgs a, const TypDev* __re
           }
           sh.crit_done = 0;
           if (prof) sh.prof[17] += __builtin_amdgcn_s_memrealtime() - t_loaded;
-          if (trace && step < a.trace_steps)
+          if (trace && step < a.trace_steps)  // (an early step's granule is out already: this word is the later one)
             trace[((size_t)blockIdx.x * a.trace_steps + step) * kTrace + 3] = __builtin_amdgcn_s_memrealtime();
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -1159,19 +1184,8 @@ __global__ __launch_bounds__(kMBlock) void k_memo(MemoArgs a, const TypDev* __re
         if (trace && lane == 0 && step < a.trace_steps)
           trace[((size_t)blockIdx.x * a.trace_steps + step) * kTrace + 2] = __builtin_amdgcn_s_memrealtime();
       }
-      const unsigned W = fresh > ex ? fresh : ex;
-      const int rk = W != 0u ? key32_rank(W) : -1;
-      // Reserve (open_gpu_share.go:178-205) on the winner: d's record is in registers
-      const int gW = key32_gpu(W);
-      const int mask = W == 0u ? -1 : (W == ex ? mask_ex : (d_gpu_from_key ? (gW < 0 ? -1 : 1 << gW) : mask_d_pre));
-      // bit 1: no feasible node at all (W == 0), as opposed to a Reserve failure on the winner
-      const unsigned pay = (W != 0u && mask >= 0) ? pack_pay(rk, mask) : (W == 0u ? 3u : 1u);
+      if (!early) publish(fresh);
       if (lane == 0) {
-        gstore32(win + step, pay);
-        asm volatile("" ::: "memory");
-        if (prof) sh.prof[20] += __builtin_amdgcn_s_memrealtime() - t_loaded;
-        if (trace && step < a.trace_steps)
-          trace[((size_t)blockIdx.x * a.trace_steps + step) * kTrace + 1] = __builtin_amdgcn_s_memrealtime();
         const int nfeas = cnt_o + (d >= 0 ? (fresh != 0u ? 1 : 0) - (old_own != 0u ? 1 : 0) : 0);
         ResultDev out{-1, 0, 0, nfeas, ST_UNSCHED};
         if (W != 0u) {
@@ -1185,7 +1199,6 @@ __global__ __launch_bounds__(kMBlock) void k_memo(MemoArgs a, const TypDev* __re
           }
         }
         gput(rp.res + step, out);
-        sh.pay = pay;
         if (prof) sh.prof[19] += __builtin_amdgcn_s_memrealtime() - t_loaded;
       }
       if (d >= 0) {  // every class of the step's score group on d (its own included)
