@@ -6,7 +6,9 @@ ratio; the replay of the extended stream equals the oracle's event for event.  T
 smallest at which the kernels can go wrong: the hand-made clusters of tests/test_desched_ref.py, a
 64-node openb subset with deleted and failed pods and three replicas of different score policies, one
 node holding more pods than a workgroup has threads, a cluster without a bound pod, and a cluster
-whose per-node tables do not fit in LDS.  Every test needs a gfx950 device.
+whose per-node tables do not fit in LDS.  All of these have an untyped typical table and equal streams in every
+replica; typed tables, ragged replicas, the stride edges of k_desched_select, both sides of its LDS / HBM switch
+and a plan on an extended stream are in tests/test_gpu_desched_fuzz.py.  Every test needs a gfx950 device.
 """
 import ctypes as C
 

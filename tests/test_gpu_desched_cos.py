@@ -6,8 +6,10 @@ replay of the extended stream equals the oracle's event for event.  The shapes a
 kernels can go wrong: the hand-made cluster of tests/test_desched_cos_ref.py, a 64-node openb subset with
 deleted and failed pods and three replicas of different score policies, one node holding more pods than a
 workgroup has threads, a cluster without a bound pod, 600 flat nodes whose order needs both sort keys over
-more nodes than a workgroup has threads, and a cluster whose per-node tables do not fit in LDS.  Every test
-needs a gfx950 device.
+more nodes than a workgroup has threads (at ratio 0.5 and, for the upper half of the sorted order, 1.0), and a
+cluster whose per-node tables do not fit in LDS.  Typed typical tables, ragged replicas, the stride edges of
+k_cos_select, both sides of its LDS / HBM switch and a plan on an extended stream are in
+tests/test_gpu_desched_fuzz.py.  Every test needs a gfx950 device.
 """
 import ctypes as C
 
@@ -116,6 +118,10 @@ def test_flat_cluster_order_needs_both_keys():
     eng.deschedule_cossim(0.5)
     got, want = got_plan(eng, 0), want_plan(case, "flat", "FGD", 0.5)
     assert got == want and len(got[0]) == got[1] == 300
+    # the whole sorted order, its upper half included
+    eng.deschedule_cossim(1.0)
+    got, want = got_plan(eng, 0), want_plan(case, "flat", "FGD", 1.0)
+    assert got == want and len(got[0]) == got[1] == 600
     eng.close()
 
 
