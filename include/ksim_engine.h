@@ -296,10 +296,37 @@ int  ksim_engine_get_nodes(ksim_engine* e, int replica, ksim_node* out);
  * report after every event of every replica (one ksim_report per event, fetched with
  * get_reports).  Disabled by default; enabling it adds two short kernels after the replay. */
 int  ksim_engine_set_report(ksim_engine* e, int enable);
+/* On an engine that is one of several shards (ksim_engine_set_shard, world > 1): KSIM_ENOTSUP, here and in
+ * get_power_reports -- a shard's rounded partial report invites an inexact sum; fetch its exact parts
+ * (ksim_engine_get_report_parts) and merge them (ksim_report_merge, ksim_shard_group_get_reports). */
 int  ksim_engine_get_reports(ksim_engine* e, int replica, ksim_report* out, int n);
 /* The per-event power report of a replica with an energy model (ksim_engine_set_power_model, any
  * policy); KSIM_ESTATE without one or while the report is disabled. */
 int  ksim_engine_get_power_reports(ksim_engine* e, int replica, ksim_power_report* out, int n);
+/* The exact per-event records behind the reports, and their merge.  Every shard of a node-sharded cluster
+ * reports the nodes it owns (an event's node term where it owns the changed node; the arrived milli on shard
+ * rank 0 only), so the cluster's record of an event is the field-by-field integer sum of the shards' records
+ * of that event, and each 128-bit sum is rounded to a double once: the report an unsharded engine gives, bit
+ * for bit, in any shard order.
+ *   ksim_engine_get_report_parts  the records of one replica of any engine with the report on, sharded or not
+ *                                 (cnt[7]: the total GPUs of the engine's nodes); KSIM_ESTATE while the report
+ *                                 is off or before a run.  The bytes are what travels between shard processes.
+ *   ksim_report_merge             host only (no device needed): event i of out / power_out from parts[k][i],
+ *                                 k < world.  KSIM_EINVAL: a null argument, world outside 1..16, n < 0.  The
+ *                                 power fields are 0 where no shard has an energy model.
+ *   ksim_shard_group_get_reports  the merged reports of the last ksim_shard_group_run of these engines, added on
+ *                                 the device (k_report_merge); arguments as ksim_shard_group_run's.  KSIM_ESTATE
+ *                                 before a group run with the report on, or for power_out without energy models. */
+typedef struct {            /* 208 bytes, the exact per-event record of one engine's nodes */
+    int64_t fx[9][2];       /* {low, high} halves of a signed 128-bit sum, LSB 2^-80: 7 frag bins, CPU W, GPU W */
+    int64_t cnt[8];         /* used nodes, used GPUs, used GPU milli, used CPU milli, arrived GPU milli,
+                               arrived CPU milli, nodes without an energy model, total GPUs of these nodes */
+} ksim_report_part;
+int  ksim_engine_get_report_parts(ksim_engine* e, int replica, ksim_report_part* out, int n);
+int  ksim_report_merge(const ksim_report_part* const* parts, int world, int n,
+                       ksim_report* out, ksim_power_report* power_out /* nullable */);
+int  ksim_shard_group_get_reports(ksim_engine* const* engines, int world,
+                                  ksim_report* out, ksim_power_report* power_out /* nullable */, int n);
 /* Device time of the report kernels of the last run (ms).  After a sequential replay: the report that
  * follows it (part of last_run_ms).  After concurrent groups: the sum over groups of each group's report
  * kernels, which run on the group's stream right behind its replay and overlap the groups still running
@@ -338,7 +365,8 @@ int  ksim_shard_group_run(ksim_engine* const* engines, int world);
  * peers' buffers (its own handle must sit at its rank: KSIM_EINVAL otherwise).  ksim_engine_run then replays
  * the shard's slices on k_hmemo and, per pod step, stores its slice maxima straight into every peer's buffer
  * (xGMI) and polls its own: selectHost over the union, the owner of the winner binds (results as above).
- * Every rank must run the same runs.  Other policies, the report or a plan that does not fit: KSIM_ENOTSUP.
+ * Every rank must run the same runs.  Other policies or a plan that does not fit: KSIM_ENOTSUP.  With the report on,
+ * each shard reports its own nodes behind its replay (ksim_engine_get_report_parts; merged by ksim_report_merge).
  * A handle is the buffer's hipIpcMemHandle_t (64 B), then "KSPH", the PCI domain / bus / device of the GPU
  * holding it and the exporting pid (u32 each), zero padded.  set_shard_peers checks, before it opens a peer
  * buffer on another GPU, that the GPU is visible here and reachable (hipDeviceCanAccessPeer): KSIM_EPEER

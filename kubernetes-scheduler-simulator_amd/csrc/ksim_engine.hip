@@ -1777,6 +1777,7 @@ __global__ __launch_bounds__(64) void k_reserve(ReplicaDev* reps, const TypDev* 
 }  // namespace
 
 #include "ksim_host.hpp"
+#include "ksim_report_host.hpp"
 
 // ---------------------------------------------------------------------------
 // Host engine object
@@ -1926,6 +1927,9 @@ struct ksim_engine {
   std::vector<DevBuf<int32_t>> d_prev;
   std::vector<DevBuf<RepAcc>> d_rep;
   std::vector<int64_t> total_gpus;
+  bool rep_ready = false;      // the records of d_rep are those of a completed run (ksim_engine_get_report_parts)
+  DevBuf<RepAcc> d_rmerge;     // a node-sharded group's merged records (engine 0 of the group; k_report_merge)
+  int rmerge_n = -1;           // events they hold (-1: no group run with the report on since the events were loaded)
   // node-sharded cluster (ksim_engine_set_shard)
   int shard_world = 0;        // 0: not sharded
   DevBuf<unsigned long long> d_ggran;  // a node-sharded group's exchange granules (engine 0 of the group)
@@ -3159,6 +3163,8 @@ static int reset_state(ksim_engine* e) {
 // Per-event report buffers of one replica (allocated while the report is enabled).
 static int alloc_report(ksim_engine* e, int r) {
   const bool on = e->report && e->d_ev[r].p;
+  e->rep_ready = false;  // (new events or the report switched: the records are no run's)
+  e->rmerge_n = -1;
   const size_t ne = (size_t)std::max(e->n_events[r], 1);
   int rc = on ? e->d_snap[r].alloc(ne) : KSIM_OK;
   if (on && !rc) rc = e->d_prev[r].alloc(ne);
@@ -3176,7 +3182,8 @@ static int run_report(ksim_engine* e, int max_ev, hipStream_t st, const int* lis
   if (max_ev <= 0 || R <= 0) return KSIM_OK;
   const dim3 grid((unsigned)((max_ev + ksim_rep::kDeltaBlock - 1) / ksim_rep::kDeltaBlock), (unsigned)R);
   hipLaunchKernelGGL(ksim_rep::k_report_delta, grid, dim3(ksim_rep::kDeltaBlock), 0, st,
-                     (const ReplicaDev*)e->d_reps.p, (const TypDev*)e->d_tp.p, list);
+                     (const ReplicaDev*)e->d_reps.p, (const TypDev*)e->d_tp.p, list,
+                     (e->shard_world > 1 && e->shard_rank != 0) ? 0 : 1);  // a cluster's arrivals: shard rank 0 counts them
   KSIM_HIP(hipGetLastError());
   // the scan over B workgroups per replica when a few replicas would leave most CUs idle behind one workgroup's pass
   // (about a CU-full of workgroups, parts of >= 2048 events; KSIM_VARIANT report_parts=0: one workgroup each)
@@ -3813,6 +3820,7 @@ int ksim_engine_run(ksim_engine* e) {
   KSIM_HIP(hipSetDevice(e->device));
   const RunEnv env = read_env();
   e->report_done = false;
+  e->rep_ready = false;
   e->ran = false;
   e->ds_plan = kDsNone;
   e->grp_rev_used = 0;
@@ -3885,6 +3893,7 @@ int ksim_engine_run(ksim_engine* e) {
     if (fail) return KSIM_ESTATE;  // a granule poll or an LDS wait timed out
   }
   e->ran = true;
+  e->rep_ready = e->report;
   return KSIM_OK;
 }
 
@@ -4049,8 +4058,8 @@ int ksim_engine_set_shard_peers(ksim_engine* e, const uint8_t* handles) {
 
 // ---- the steps the node-sharded runs share ----
 // One shard back to its initial state, enqueued on `st`: the node records and tag counts, the report's last-event
-// table when the report is on (the k_step path only: no replay kernel of a shard reports), and with `results` the
-// result records (the replay kernels write a result only where a shard has one to report).
+// table when the report is on (k_step's; the replay kernels keep theirs in LDS and reset it as they start), and with
+// `results` the result records (the replay kernels write a result only where a shard has one to report).
 static int reset_shard_state(ksim_engine* e, hipStream_t st, bool results) {
   KSIM_HIP(hipMemcpyAsync(e->d_nodes.p, e->d_nodes_init.p, sizeof(NodeRec) * (size_t)e->N, hipMemcpyDeviceToDevice, st));
   KSIM_HIP(hipMemcpyAsync(e->d_tags.p, e->d_tags_init.p, sizeof(uint16_t) * e->tags_stride, hipMemcpyDeviceToDevice, st));
@@ -4063,16 +4072,54 @@ static int reset_shard_state(ksim_engine* e, hipStream_t st, bool results) {
 // The end of an in-process group's run on engine 0's stream: the closing event, the wait, the fail word of the
 // group's one launch, then the run's time and diagnostics on every engine.  K = 0: the per-pod k_step path, which
 // has no fail word and no width.
+//
+// With the cluster report on (every shard or none: ksim_shard_group_run checks), the report follows the replay once
+// its fail word is read clean (a replay that gave up leaves events without a snapshot): every shard's own report
+// (run_report: its nodes' terms, the arrivals on shard 0) and the merge of the shards' records into engine 0's
+// d_rmerge (k_report_merge), all on the group's stream.  last_report_ms on every engine is the time of all of that;
+// last_ms includes it, as ksim_engine_run's does.  Without the report the run ends as it always did.
 static int finish_group_run(ksim_engine* const* engines, int world, int max_ev, int K, const char* kernel, bool hmemo) {
   ksim_engine* e0 = engines[0];
-  KSIM_HIP(hipEventRecord(e0->ev1, e0->stream));
-  KSIM_HIP(hipStreamSynchronize(e0->stream));
+  hipStream_t st = e0->stream;
+  const bool report = e0->report;
+  KSIM_HIP(hipEventRecord(report ? e0->ev_mid : e0->ev1, st));
+  KSIM_HIP(hipStreamSynchronize(st));
   int fail = 0;
   if (K > 0) KSIM_HIP(hipMemcpy(&fail, e0->d_fail.p, sizeof(int), hipMemcpyDeviceToHost));
   if (fail) return KSIM_ESTATE;
+  float rms = 0;
+  if (report) {
+    int rc;
+    ksim_rep::MergeArgs ma{};
+    for (int k = 0; k < world; ++k) {
+      if ((rc = run_report(engines[k], max_ev, st, nullptr, 1))) return rc;
+      ma.part[k] = engines[k]->d_rep[0].p;
+    }
+    if ((rc = e0->d_rmerge.ensure((size_t)std::max(max_ev, 1)))) return rc;
+    const bool times = read_env().group_times;  // KSIM_GROUP_TIMES=1: the merge's share of the report, on stderr
+    if (times) {
+      if ((rc = e0->tev_fork.ensure())) return rc;
+      KSIM_HIP(hipEventRecord(e0->tev_fork, st));
+    }
+    if (max_ev > 0) {
+      const long long lanes = (long long)max_ev * ksim_rep::kMergeLanes;
+      hipLaunchKernelGGL(ksim_rep::k_report_merge, dim3((unsigned)((lanes + ksim_rep::kMergeBlock - 1) / ksim_rep::kMergeBlock)),
+                         dim3(ksim_rep::kMergeBlock), 0, st, ma, world, max_ev, e0->d_rmerge.p);
+      KSIM_HIP(hipGetLastError());
+    }
+    KSIM_HIP(hipEventRecord(e0->ev1, st));
+    KSIM_HIP(hipStreamSynchronize(st));
+    KSIM_HIP(hipEventElapsedTime(&rms, e0->ev_mid, e0->ev1));
+    e0->rmerge_n = max_ev;
+    float mms = 0;
+    if (times && hipEventElapsedTime(&mms, e0->tev_fork, e0->ev1) == hipSuccess)
+      std::fprintf(stderr, "ksim group report times (ms): %d shards' reports %.3f; merge %.3f\n", world, rms - mms, mms);
+  }
   float ms = 0;
   KSIM_HIP(hipEventElapsedTime(&ms, e0->ev0, e0->ev1));
   for (int k = 0; k < world; ++k) {
+    engines[k]->last_report_ms = rms;
+    engines[k]->rep_ready = report;
     engines[k]->last_ms = ms;
     engines[k]->last_steps = max_ev;
     if (K > 0) engines[k]->last_K = K;
@@ -4086,8 +4133,7 @@ static int finish_group_run(ksim_engine* const* engines, int world, int max_ev, 
 // shard's workgroups (K per shard, the same K and S on every rank: from n_global and world only).
 static int run_hmemo_peer(ksim_engine* e, const RunEnv& env, int max_ev) {
   using namespace ksim_hmemo;
-  if (e->R != 1 || e->reps[0].policy != POL_FGD || e->report || go_random(e, 0) || !score_table())
-    return KSIM_ENOTSUP;
+  if (e->R != 1 || e->reps[0].policy != POL_FGD || go_random(e, 0) || !score_table()) return KSIM_ENOTSUP;
   const int world = e->shard_world;
   const ShardSlices sl = hmemo_peer_slices(e->n_global, world, e->N);
   if (!sl.ok) return KSIM_ENOTSUP;
@@ -4149,8 +4195,7 @@ static bool hmemo_group_eligible(ksim_engine* const* engines, int world, const R
   if (!score_table()) return false;
   for (int k = 0; k < world; ++k) {
     const ksim_engine* e = engines[k];
-    if (e->R != 1 || e->reps[0].policy != POL_FGD || e->report || e->run_mode == 1 || e->run_mode == 2 ||
-        go_random(e, 0))
+    if (e->R != 1 || e->reps[0].policy != POL_FGD || e->run_mode == 1 || e->run_mode == 2 || go_random(e, 0))
       return false;
   }
   return true;
@@ -4159,15 +4204,14 @@ static bool hmemo_group_eligible(ksim_engine* const* engines, int world, const R
 // The cheap policies' node-sharded group on k_replay slices (r06, round-5 verdict item 7): every shard's K slices in
 // ONE launch, one exchange of Kt = world x K columns per pod step (the keys carry global name ranks, so the max is
 // selectHost over the union, generic_scheduler.go:187-212; BestFit's NormalizeScore range rides in the same granules
-// as in the unsharded k_replay, plugin_utils.go:48-74).  Lean runs only: one replica per shard,
-// a create-only stream, no report, no profile.
+// as in the unsharded k_replay, plugin_utils.go:48-74).  One replica per shard, a create-only stream, no profile;
+// with the cluster report on, the general instantiation (its report stores) where its layout fits.
 static bool replay_group_eligible(ksim_engine* const* engines, int world, const RunEnv& env) {
   const int pol = engines[0]->reps[0].policy;
   if (pol < POL_BESTFIT || pol > POL_RANDOM || variant("shard_replay", 1) == 0) return false;
   for (int k = 0; k < world; ++k) {
     const ksim_engine* e = engines[k];
-    if (e->R != 1 || e->reps[0].policy != pol || e->report || e->run_mode == 1 || e->has_delete[0] || go_random(e, 0))
-      return false;
+    if (e->R != 1 || e->reps[0].policy != pol || e->run_mode == 1 || e->has_delete[0] || go_random(e, 0)) return false;
   }
   return env.profile == 0;
 }
@@ -4183,9 +4227,10 @@ static int run_replay_group(ksim_engine* const* engines, int world, const RunEnv
   const ShardSlices sl = replay_group_slices(N, world, e0->cus, pol);
   if (!sl.ok) return KSIM_OK;
   const int K = sl.K, S = sl.S, Kt = world * K;
-  const void* f = replay_kernel(pol, Kt, false);
-  const size_t lds = replay::replay_lds(S, pol, false);
-  if (Kt > resident_cap(e0, f, lds)) return KSIM_OK;
+  const bool general = e0->report;  // the report stores (snap / prev) are the general instantiation's
+  const void* f = replay_kernel(pol, Kt, general);
+  const size_t lds = replay::replay_lds(S, pol, general);
+  if (lds > kLdsMax || Kt > resident_cap(e0, f, lds)) return KSIM_OK;
   hipStream_t st = e0->stream;
   KSIM_HIP(hipSetDevice(e0->device));
   int rc;
@@ -4297,9 +4342,12 @@ int ksim_shard_group_run(ksim_engine* const* engines, int world) {
         !e->d_ev[0].p)
       return KSIM_EINVAL;
     if (e->n_events[0] != e0->n_events[0]) return KSIM_EINVAL;  // every shard sees the same events
+    if (e->report != e0->report) return KSIM_EINVAL;            // and reports, or none does: the records are merged
     max_ev = std::max(max_ev, e->n_events[0]);
   }
   KSIM_HIP(hipSetDevice(e0->device));
+  for (int k = 0; k < world; ++k) engines[k]->rep_ready = false;
+  e0->rmerge_n = -1;
   const RunEnv env = read_env();
   if (hmemo_group_eligible(engines, world, env)) {
     bool done = false;
@@ -4335,8 +4383,6 @@ int ksim_shard_group_run(ksim_engine* const* engines, int world) {
     for (int k = 0; k < world; ++k)
       if ((rc = shard_commit(engines[k], st, nullptr, s))) return rc;
   }
-  for (int k = 0; k < world; ++k)
-    if (engines[k]->report && (rc = run_report(engines[k], max_ev, engines[k]->stream, nullptr, engines[k]->R))) return rc;
   return finish_group_run(engines, world, max_ev, 0, "k_step", false);
 }
 
@@ -4356,6 +4402,7 @@ int ksim_engine_set_report(ksim_engine* e, int enable) {
 
 int ksim_engine_get_reports(ksim_engine* e, int replica, ksim_report* out, int n) {
   if (!e || !out || replica < 0 || replica >= e->R || n < 0 || n > e->n_events[replica]) return KSIM_EINVAL;
+  if (e->shard_world > 1) return KSIM_ENOTSUP;  // one shard's nodes only: ksim_engine_get_report_parts, merged
   if (!e->report || !e->d_rep[replica].p) return KSIM_ESTATE;
   if (n == 0) return KSIM_OK;
   std::vector<RepAcc> h((size_t)n);
@@ -4380,6 +4427,7 @@ int ksim_engine_get_reports(ksim_engine* e, int replica, ksim_report* out, int n
 
 int ksim_engine_get_power_reports(ksim_engine* e, int replica, ksim_power_report* out, int n) {
   if (!e || !out || replica < 0 || replica >= e->R || n < 0 || n > e->n_events[replica]) return KSIM_EINVAL;
+  if (e->shard_world > 1) return KSIM_ENOTSUP;
   if (!e->report || !e->d_rep[replica].p || !e->pw_set[replica]) return KSIM_ESTATE;
   if (n == 0) return KSIM_OK;
   std::vector<RepAcc> h((size_t)n);
@@ -4393,6 +4441,53 @@ int ksim_engine_get_power_reports(ksim_engine* e, int replica, ksim_power_report
     o.cluster_w = o.cpu_w + o.gpu_w;  // analysis.go:54 powerCPUCluster + powerGPUCluster
     o.invalid_nodes = h[i].cnt[6];
   }
+  return KSIM_OK;
+}
+
+// The exact records (ksim_report_part is RepAcc byte for byte; ksim_report_host.hpp turns them into reports).
+static_assert(sizeof(ksim_report_part) == sizeof(RepAcc) && offsetof(ksim_report_part, cnt) == offsetof(RepAcc, cnt),
+              "ksim_report_part must match RepAcc");
+static_assert(ksim_rep::kMaxWorld == ksim_rep_host::kMaxWorld && ksim_rep::kFx == ksim_rep_host::kFx, "report limits");
+
+// n records of `src` (device) into out, cnt[7] = total_gpus on each.
+static int fetch_parts(ksim_engine* e, const RepAcc* src, ksim_report_part* out, int n, int64_t total_gpus) {
+  if (n == 0) return KSIM_OK;
+  KSIM_HIP(hipSetDevice(e->device));
+  KSIM_HIP(hipMemcpyAsync(out, src, sizeof(RepAcc) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipStreamSynchronize(e->stream));
+  for (int i = 0; i < n; ++i) out[i].cnt[7] = total_gpus;
+  return KSIM_OK;
+}
+
+int ksim_engine_get_report_parts(ksim_engine* e, int replica, ksim_report_part* out, int n) {
+  if (!e || !out || replica < 0 || replica >= e->R || n < 0 || n > e->n_events[replica]) return KSIM_EINVAL;
+  if (!e->report || !e->rep_ready || !e->d_rep[replica].p) return KSIM_ESTATE;
+  return fetch_parts(e, e->d_rep[replica].p, out, n, e->total_gpus[replica]);
+}
+
+int ksim_report_merge(const ksim_report_part* const* parts, int world, int n, ksim_report* out,
+                      ksim_power_report* power_out) {
+  return ksim_rep_host::merge(parts, world, n, out, power_out);
+}
+
+int ksim_shard_group_get_reports(ksim_engine* const* engines, int world, ksim_report* out, ksim_power_report* power_out,
+                                 int n) {
+  if (!engines || !out || world < 1 || world > 16 || n < 0) return KSIM_EINVAL;
+  ksim_engine* e0 = engines[0];
+  int64_t total = 0;
+  bool ready = true, pw = true;
+  for (int k = 0; k < world; ++k) {
+    const ksim_engine* e = engines[k];
+    if (!e || e->shard_world != world || e->shard_rank != k || e->comm || e->xfn || e->device != e0->device) return KSIM_EINVAL;
+    ready = ready && e->report && e->rep_ready;
+    pw = pw && e->pw_set[0];
+    total += e->total_gpus[0];
+  }
+  if (!ready || e0->rmerge_n < 0 || (power_out && !pw)) return KSIM_ESTATE;
+  if (n > e0->rmerge_n) return KSIM_EINVAL;
+  std::vector<ksim_report_part> h((size_t)n);
+  if (int rc = fetch_parts(e0, e0->d_rmerge.p, h.data(), n, total)) return rc;
+  for (int i = 0; i < n; ++i) ksim_rep_host::part_reports(h[i], out + i, power_out ? power_out + i : nullptr);
   return KSIM_OK;
 }
 

@@ -20,6 +20,9 @@
 // independent: the cluster bins are the correctly rounded exact sum of the per-node fp64 bins,
 // whatever the node order (the reference's order is a Go map's, so it is not reproducible; the
 // contract is 1e-9 relative, DESIGN.md "Cluster report").  None of this is on the per-pod path.
+// For the same reason the shards of a node-sharded cluster each report their own nodes and the records add up:
+//   k_report_merge  one thread per 16 bytes of a record: the sum of the shards' prefix records (in-process group);
+//   between processes the same integer sum runs on the host (ksim_report_host.hpp).
 #pragma once
 
 namespace ksim_rep {
@@ -84,23 +87,30 @@ __device__ __forceinline__ void store_rep(RepAcc* o, const __int128 (&f)[kFields
 }
 
 // The report delta of event e of a replica (s_tp: its typical table in LDS).
-__device__ __forceinline__ void report_delta_event(const ReplicaDev& rp, const TypDev* s_tp, int e) {
+// A node-sharded replica holds the nodes of global name ranks [node_off, node_off + n_local): results carry global
+// ranks (finish_cycle, k_replay's and k_hmemo's group forms), and the shard takes an event's node term only where it
+// owns the node -- the owner is the one that stored snap[e] / prev[e]; a shard that does not own the winner holds a
+// provisional record and no snapshot.  The deletion of a pod bound in another shard, a create no node can host and a
+// Reserve failure add no node term here.  Unsharded, node_off is 0 and n_local is N.  `arrivals`: this replica counts
+// the event's arrived milli (fields 13, 14) -- shard rank 0 only, so that the shards' records add up to the cluster's.
+__device__ __forceinline__ void report_delta_event(const ReplicaDev& rp, const TypDev* s_tp, int e, bool arrivals) {
   __int128 d[kFields];
 #pragma unroll
   for (int k = 0; k < kFields; ++k) d[k] = 0;
   const PodDev p = rp.ev[e];
   const ResultDev res = rp.res[e];
-  if (!(p.flags & kPodDelete)) {
+  if (arrivals && !(p.flags & kPodDelete)) {
     d[13] = (long long)p.milli * (long long)p.num;  // PodResource.TotalMilliGpu (resource.go:129-131)
     d[14] = p.cpu_nz;                               // PodResource.MilliCpu
   }
-  if (res.node >= 0 && (res.status == ST_OK || res.status == ST_DELETED)) {
+  const int local = res.node - rp.node_off;
+  if (res.node >= 0 && local >= 0 && local < rp.n_local && (res.status == ST_OK || res.status == ST_DELETED)) {
     const int pv = rp.prev[e];
     const NodeV after = load_node(rp.snap + e);
-    const NodeV before = load_node(pv >= 0 ? rp.snap + pv : rp.init + res.node);
-    const int cap = rp.cap[res.node];
+    const NodeV before = load_node(pv >= 0 ? rp.snap + pv : rp.init + local);
+    const int cap = rp.cap[local];
     const PowerDev* pw = rp.has_pw ? rp.pw : nullptr;
-    const int cm = rp.cpum[res.node];
+    const int cm = rp.cpum[local];
     __int128 a[kFields], b[kFields];
     node_term(after, cap, s_tp, rp.ncpu, rp.nt, pw, cm, a);
     node_term(before, cap, s_tp, rp.ncpu, rp.nt, pw, cm, b);
@@ -113,7 +123,7 @@ __device__ __forceinline__ void report_delta_event(const ReplicaDev& rp, const T
 
 // grid (ceil(E_max / kDeltaBlock), R): the report delta of every event.
 __global__ __launch_bounds__(kDeltaBlock) void k_report_delta(const ReplicaDev* reps, const TypDev* __restrict__ tp_all,
-                                                              const int* list) {
+                                                              const int* list, int arrivals) {
   const int r = list ? list[blockIdx.y] : (int)blockIdx.y;  // list: one concurrent group's replicas
   const ReplicaDev rp = reps[r];
   if (!rp.rep) return;
@@ -121,7 +131,7 @@ __global__ __launch_bounds__(kDeltaBlock) void k_report_delta(const ReplicaDev* 
   stage_typical(tp_all + (size_t)r * kMaxTypical, rp.nt, s_tp);
   const int e = (int)blockIdx.x * kDeltaBlock + (int)threadIdx.x;
   if (e >= rp.n_events) return;
-  report_delta_event(rp, s_tp, e);
+  report_delta_event(rp, s_tp, e, arrivals != 0);
 }
 
 __device__ __forceinline__ __int128 shfl_up128(__int128 v, int o) {
@@ -345,12 +355,42 @@ __global__ __launch_bounds__(kScanBlock) void k_report_overlap(const ReplicaDev*
     const ReplicaDev rp = reps[r];
     if (rp.rep) {
       stage_typical(tp_all + (size_t)r * kMaxTypical, rp.nt, s_tp);
-      for (int e = (int)threadIdx.x; e < rp.n_events; e += kScanBlock) report_delta_event(rp, s_tp, e);
+      for (int e = (int)threadIdx.x; e < rp.n_events; e += kScanBlock) report_delta_event(rp, s_tp, e, true);
       __syncthreads();
       report_scan_replica(rp, s_tp, N);
     }
     __syncthreads();  // (s_b, s_tp and the scan's LDS are reused by the next replica)
   }
+}
+
+// The cluster report of a node-sharded in-process group: record e of `out` is the field-by-field sum of the `world`
+// shards' record e (each the shard's own prefix sum, k_report_scan / k_report_apply).  A RepAcc is 13 16-byte lanes: 9
+// signed 128-bit sums (added as __int128: the carry goes from the low half to the high one) and 4 pairs of 64-bit
+// counters (added as int64 each).  One thread a lane of one event, so a wave reads 1 KiB of each shard's stream
+// contiguously; grid ceil(13 n / kMergeBlock).  Integer adds: the sum is exact and the same in any shard order.
+constexpr int kMergeBlock = 256;
+constexpr int kMergeLanes = (int)(sizeof(RepAcc) / 16);
+constexpr int kMaxWorld = 16;
+struct MergeArgs {
+  const RepAcc* part[kMaxWorld];
+};
+__global__ __launch_bounds__(kMergeBlock) void k_report_merge(MergeArgs a, int world, int n, RepAcc* out) {
+  static_assert(sizeof(RepAcc) == 13 * 16 && kFx == 9, "RepAcc: 9 128-bit lanes, then 4 lanes of two counters");
+  const long long t = (long long)blockIdx.x * kMergeBlock + (long long)threadIdx.x;
+  if (t >= (long long)n * kMergeLanes) return;
+  const bool wide = (int)(t % kMergeLanes) < kFx;
+  unsigned __int128 s = 0;
+  unsigned long long c0 = 0, c1 = 0;  // (two's complement: the unsigned sums are the signed counters' sums)
+  for (int k = 0; k < world; ++k) {
+    const ulonglong2 v = reinterpret_cast<const ulonglong2*>(a.part[k])[t];
+    s += ((unsigned __int128)v.y << 64) | v.x;
+    c0 += v.x;
+    c1 += v.y;
+  }
+  ulonglong2 o;
+  o.x = wide ? (unsigned long long)s : c0;
+  o.y = wide ? (unsigned long long)(s >> 64) : c1;
+  reinterpret_cast<ulonglong2*>(out)[t] = o;
 }
 
 }  // namespace ksim_rep

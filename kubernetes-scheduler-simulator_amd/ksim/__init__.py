@@ -103,6 +103,11 @@ class PowerReport(C.Structure):
                 ("invalid_nodes", C.c_int64)]
 
 
+class ReportPart(C.Structure):
+    """ksim_report_part: the exact per-event record of one engine's nodes (Engine.report_parts)."""
+    _fields_ = [("fx", (C.c_int64 * 2) * 9), ("cnt", C.c_int64 * 8)]
+
+
 class Config(C.Structure):
     _fields_ = [("device", C.c_int32), ("nodes_per_block", C.c_int32), ("steps_per_graph", C.c_int32),
                 ("wgs_per_replica", C.c_int32), ("run_mode", C.c_int32), ("reserved", C.c_int32 * 3)]
@@ -147,7 +152,7 @@ COS_CPU_BAR_MILLI, COS_GPU_BAR_MILLI = 2000, 500
 
 assert C.sizeof(Node) == 128 and C.sizeof(Pod) == 48 and C.sizeof(Typical) == 32 and C.sizeof(Result) == 24
 assert C.sizeof(Report) == 112 and C.sizeof(PowerReport) == 32 and C.sizeof(Victim) == 40
-assert C.sizeof(CosVictim) == 32
+assert C.sizeof(CosVictim) == 32 and C.sizeof(ReportPart) == 208
 
 _LIB = None
 
@@ -191,6 +196,9 @@ SIGNATURES = {
     "ksim_engine_get_reports": (C.c_int, [_VP, C.c_int, _P(Report), C.c_int]),
     "ksim_engine_get_power_reports": (C.c_int, [_VP, C.c_int, _P(PowerReport), C.c_int]),
     "ksim_engine_last_report_ms": (C.c_int, [_VP, _P(C.c_double)]),
+    "ksim_engine_get_report_parts": (C.c_int, [_VP, C.c_int, _P(ReportPart), C.c_int]),
+    "ksim_report_merge": (C.c_int, [_P(_P(ReportPart)), C.c_int, C.c_int, _P(Report), _P(PowerReport)]),
+    "ksim_shard_group_get_reports": (C.c_int, [_P(_VP), C.c_int, _P(Report), _P(PowerReport), C.c_int]),
     "ksim_shard_comm_id": (C.c_int, [_P(C.c_uint8)]),
     "ksim_engine_set_shard": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_uint8)]),
     "ksim_shard_group_run": (C.c_int, [_P(_VP), C.c_int]),
@@ -647,10 +655,16 @@ class Engine:
         n = self.n_events[r]
         out = (Report * max(1, n))()
         check(lib().ksim_engine_get_reports(self.h, r, out, n), "get_reports")
-        return [dict(frag_bins=list(out[i].frag_bins), used_nodes=out[i].used_nodes, used_gpus=out[i].used_gpus,
-                     used_gpu_milli=out[i].used_gpu_milli, total_gpus=out[i].total_gpus,
-                     arrived_gpu_milli=out[i].arrived_gpu_milli, used_cpu_milli=out[i].used_cpu_milli,
-                     arrived_cpu_milli=out[i].arrived_cpu_milli) for i in range(n)]
+        return self._report_dicts(out, n)
+
+    def report_parts(self, r):
+        """The exact per-event records of replica r (a ksim.ReportPart array; ksim_engine_get_report_parts), on a
+        sharded engine those of its own nodes.  bytes() of it is what travels between shard processes;
+        ksim.report_merge adds the shards' parts into the cluster's reports."""
+        n = self.n_events[r]
+        out = (ReportPart * max(1, n))()
+        check(lib().ksim_engine_get_report_parts(self.h, r, out, n), "get_report_parts")
+        return (ReportPart * n).from_buffer_copy(bytes(out)[: n * C.sizeof(ReportPart)])
 
     def report_arrays(self, r):
         """The reports of replica r as numpy arrays (frag_bins [n,7] float64, counters [n] int64)."""
@@ -670,6 +684,17 @@ class Engine:
         n = self.n_events[r]
         out = (PowerReport * max(1, n))()
         check(lib().ksim_engine_get_power_reports(self.h, r, out, n), "get_power_reports")
+        return self._power_dicts(out, n)
+
+    @staticmethod
+    def _report_dicts(out, n):
+        return [dict(frag_bins=list(out[i].frag_bins), used_nodes=out[i].used_nodes, used_gpus=out[i].used_gpus,
+                     used_gpu_milli=out[i].used_gpu_milli, total_gpus=out[i].total_gpus,
+                     arrived_gpu_milli=out[i].arrived_gpu_milli, used_cpu_milli=out[i].used_cpu_milli,
+                     arrived_cpu_milli=out[i].arrived_cpu_milli) for i in range(n)]
+
+    @staticmethod
+    def _power_dicts(out, n):
         return [dict(cluster_w=out[i].cluster_w, cpu_w=out[i].cpu_w, gpu_w=out[i].gpu_w,
                      invalid_nodes=out[i].invalid_nodes) for i in range(n)]
 
@@ -828,6 +853,39 @@ def shard_group_run(engines):
     ms = C.c_double(0)
     check(lib().ksim_engine_last_run_ms(engines[0].h, C.byref(ms)), "last_run_ms")
     return ms.value
+
+
+def report_merge(parts_list):
+    """(reports, power_reports) of a cluster from its shards' exact records (ksim_report_merge, on the host: no
+    device needed): parts_list holds one entry per shard, an Engine.report_parts() array or its bytes(), all of the
+    same length.  The records are added as 128-bit integers and rounded once, so the reports are those of an
+    unsharded engine, in the dict shapes of Engine.reports / Engine.power_reports."""
+    arrs = []
+    for p in parts_list:
+        if isinstance(p, (bytes, bytearray, memoryview)):
+            b = bytes(p)
+            if len(b) % C.sizeof(ReportPart):
+                raise ValueError("report parts: not a whole number of 208-byte records")
+            p = (ReportPart * (len(b) // C.sizeof(ReportPart))).from_buffer_copy(b)
+        arrs.append(p)
+    if not arrs or any(len(a) != len(arrs[0]) for a in arrs):
+        raise ValueError("report parts: one array per shard, all of the same length")
+    n, world = len(arrs[0]), len(arrs)
+    ptrs = (_P(ReportPart) * world)(*[C.cast(a, _P(ReportPart)) for a in arrs])
+    out, pw = (Report * max(1, n))(), (PowerReport * max(1, n))()
+    check(lib().ksim_report_merge(ptrs, world, n, out, pw), "report_merge")
+    return Engine._report_dicts(out, n), Engine._power_dicts(pw, n)
+
+
+def shard_group_reports(engines, power=False):
+    """The merged reports (power=True: power reports) of the last shard_group_run of `engines`, added on the device
+    (ksim_shard_group_get_reports)."""
+    arr = (_VP * len(engines))(*[e.h for e in engines])
+    n = engines[0].n_events[0]
+    out = (Report * max(1, n))()
+    pw = (PowerReport * max(1, n))() if power else None
+    check(lib().ksim_shard_group_get_reports(arr, len(engines), out, pw, n), "shard_group_get_reports")
+    return Engine._power_dicts(pw, n) if power else Engine._report_dicts(out, n)
 
 
 def make_pod(cpu, milli=0, num=0, mem=0, type_mask=KSIM_TYPE_ANY, cpu_nz=None):

@@ -46,10 +46,19 @@ def merge_results(per_shard, parts):
     return out
 
 
-class ShardGroup:
-    """`world` shards of one cluster on one device, run in lockstep (ksim_shard_group_run)."""
+def merge_reports(parts_per_shard):
+    """(reports, power_reports) of the cluster from one Engine.report_parts() array (or its bytes) per shard:
+    ksim.report_merge, the exact integer sum rounded once."""
+    return ksim.report_merge(parts_per_shard)
 
-    def __init__(self, nodes, typical, world, policy="FGD", seed=0, device=0, report=False):
+
+class ShardGroup:
+    """`world` shards of one cluster on one device, run in lockstep (ksim_shard_group_run).
+    report=True: every shard reports its own nodes after the replay and the records are merged on the device
+    (reports() / power_reports(); report_parts() gives each shard's exact records).  power_model: the energy
+    model of the [Power] report, set on every shard."""
+
+    def __init__(self, nodes, typical, world, policy="FGD", seed=0, device=0, report=False, power_model=None):
         arr, n = typical
         self.parts = partition(nodes, world)
         self.engines = []
@@ -59,6 +68,8 @@ class ShardGroup:
             e.set_nodes(0, local)
             e.set_typical(0, arr, n)
             e.set_policy(0, policy, seed=seed)
+            if power_model is not None:
+                e.set_power_model(0, power_model)
             if report:
                 e.set_report(True)
             self.engines.append(e)
@@ -72,6 +83,18 @@ class ShardGroup:
 
     def results(self):
         return merge_results([e.results(0) for e in self.engines], self.parts)
+
+    def reports(self):
+        """The cluster's report after every event, merged on the device (dicts as Engine.reports)."""
+        return ksim.shard_group_reports(self.engines)
+
+    def power_reports(self):
+        """The cluster's [Power] report after every event (needs power_model)."""
+        return ksim.shard_group_reports(self.engines, power=True)
+
+    def report_parts(self):
+        """Each shard's exact per-event records (Engine.report_parts), in shard order."""
+        return [e.report_parts(0) for e in self.engines]
 
     def close(self):
         for e in self.engines:
@@ -96,7 +119,7 @@ def host_gather(dist, group=None):
 
 
 def run_distributed(nodes, typical, events, n, dist, policy="FGD", seed=0, device=0, engine_cls=None,
-                    exchange="rccl"):
+                    exchange="rccl", report=False, power_model=None):
     """One shard per process (torchrun; backend nccl = RCCL for the launcher's own collectives):
     rank 0 makes the RCCL id of the shards' exchange, every rank builds its shard engine on
     `device`, replays the events, and the per-shard results are gathered and merged on every rank.
@@ -104,7 +127,10 @@ def run_distributed(nodes, typical, events, n, dist, policy="FGD", seed=0, devic
     e.g. shards sharing one GPU, or hosts without a common RCCL fabric.
     exchange="device" (FGD): each shard's persistent k_hmemo stores its per-step slice maxima straight into
     every peer's IPC-mapped exchange buffer (ksim_engine_set_shard_peers); `dist` only carries the handles.
-    Returns (merged results, device ms of this rank's run)."""
+    report=True: every shard also reports its own nodes; the ranks gather the exact records (all_gather_object of
+    their bytes) and each merges them on the host (merge_reports).  power_model: the [Power] report's energy model.
+    Returns (merged results, device ms of this rank's run), with report=True (merged results, ms, reports): the
+    cluster's report per event, each with its power report under "power" when a power_model was given."""
     engine_cls = engine_cls or ksim.Engine
     rank, world = dist.get_rank(), dist.get_world_size()
     parts = partition(nodes, world)
@@ -128,13 +154,27 @@ def run_distributed(nodes, typical, events, n, dist, policy="FGD", seed=0, devic
     arr, nt = typical
     e.set_typical(0, arr, nt)
     e.set_policy(0, policy, seed=seed)
+    if power_model is not None:
+        e.set_power_model(0, power_model)
+    if report:
+        e.set_report(True)
     e.load_events(0, events, n)
     ms = e.run()
     mine = e.results(0)
+    my_parts = bytes(e.report_parts(0)) if report else None
     e.close()
     gathered = [None] * world
     dist.all_gather_object(gathered, mine)
-    return merge_results(gathered, parts), ms
+    merged = merge_results(gathered, parts)
+    if not report:
+        return merged, ms
+    all_parts = [None] * world
+    dist.all_gather_object(all_parts, my_parts)
+    reports, power = merge_reports(all_parts)
+    if power_model is not None:
+        for r, p in zip(reports, power):
+            r["power"] = p
+    return merged, ms, reports
 
 
 def shard_comm_id_for(engine_cls):
