@@ -11,7 +11,8 @@
 //   k_desched_select  one workgroup per replica: the pop / pick / re-key loop of the policy over those
 //                     values, victims in eviction order.
 // The cosSim policy (:49-92; the victim of one node: findVictimPodOnCosSim, deschedule_utils.go:15-45) shares
-// k_desched_mark and has k_cos_eval and k_cos_select of its own, at the end of this file.
+// k_desched_mark and has k_cos_eval and k_cos_select of its own, at the end of this file.  The host side is one
+// driver for all policies: desched_plan in ksim_engine.hip, its arithmetic in ksim_desched_host.hpp.
 // The rescheduling itself is the ordinary replay of the extended event stream (ksim/desched.py).
 // No kernel here waits for another workgroup, and nothing is on the per-pod path.
 //
@@ -113,27 +114,30 @@ static_assert(sizeof(ksim_victim) == 40, "ksim_victim layout");
 constexpr int kEvalBlock = 256;
 constexpr int kSelBlock = 256;
 constexpr int kSelNodeBytes = 20;          // per-node tables of k_desched_select: key 8, rank 4, start 4, end 4
-constexpr int kSelLdsBytes = 60 * 1024;    // they sit in LDS up to this size (3072 nodes), in HBM beyond
+constexpr int kSelLdsBytes = 60 * 1024;    // a select kernel's tables sit in LDS up to this size, in HBM beyond
 // one replica's tables in HBM: 16-byte aligned, so the 8-byte keys at its start are aligned for any N
-KSIM_HD size_t sel_tab_stride(int N) { return ((size_t)N * kSelNodeBytes + 15) & ~(size_t)15; }
+KSIM_HD size_t tab_stride(int N, int node_bytes) { return ((size_t)N * node_bytes + 15) & ~(size_t)15; }
 
-struct DsArgs {
+struct PlanArgs {          // what the kernels of every policy take
   const ReplicaDev* reps;
   const long long* eoff;   // [R + 1] first event slot of each replica in the per-event buffers
-  EvalRec* eval;           // [Σ E]
-  uint8_t* gone;           // [Σ E] creation events whose delete took effect
-  int32_t* plist;          // [Σ E] k_desched_select: candidate events grouped by node
-  ksim_victim* vict;       // [Σ E]
+  uint8_t* gone;           // [Σ E] creation events whose delete took effect (k_desched_mark)
   int32_t* bound;          // [R] pods still bound
   const int32_t* budget;   // [R]
   int32_t* n_vict;         // [R]
-  uint8_t* tab;            // [R][sel_tab_stride(N)] the per-node tables when they do not fit in LDS, else null
+  uint8_t* tab;            // [R][tab_stride(N, its bytes per node)] the select kernel's tables beyond LDS, else null
   int N;
+};
+
+struct DsArgs : PlanArgs {
+  EvalRec* eval;           // [Σ E]
+  int32_t* plist;          // [Σ E] k_desched_select: candidate events grouped by node
+  ksim_victim* vict;       // [Σ E]
   int policy;              // ksim_desched_policy
 };
 
 // grid (ceil(E_max / kEvalBlock), R): gone[ref] = 1 for every delete event that took effect.
-__global__ __launch_bounds__(kEvalBlock) void k_desched_mark(DsArgs a) {
+__global__ __launch_bounds__(kEvalBlock) void k_desched_mark(PlanArgs a) {
   const int r = (int)blockIdx.y;
   const ReplicaDev rp = a.reps[r];
   const int e = (int)blockIdx.x * kEvalBlock + (int)threadIdx.x;
@@ -141,6 +145,33 @@ __global__ __launch_bounds__(kEvalBlock) void k_desched_mark(DsArgs a) {
   const PodDev p = rp.ev[e];
   if (!(p.flags & kPodDelete) || rp.res[e].status != ST_DELETED) return;
   if (p.ref >= 0 && p.ref < e) a.gone[a.eoff[r] + p.ref] = 1;
+}
+
+// The opening of both eval kernels, for event e (< n_events) of replica r: returns whether its pod is still bound
+// and, when the result record validates, calls body(node, its unpacked GPU-left array) inside the two tests, as the
+// kernels had it inline (the compiler's output is the same).  The record is validated before it indexes anything:
+// the node index before the node is loaded, the mask against the node's GPU count before anything uses it.
+template <class F>
+__device__ __forceinline__ bool eval_bound_node(const PlanArgs& a, const ReplicaDev& rp, int r, int e, const PodDev& p,
+                                                const ResultDev& res, F&& body) {
+  const bool bound = !(p.flags & kPodDelete) && res.status == ST_OK && !a.gone[a.eoff[r] + e];
+  if (bound && res.node >= 0 && res.node < a.N && res.gpu_mask >= 0) {
+    const NodeV n = load_node(rp.nodes + res.node);
+    const int cnt = n.gpu_cnt();
+    if (cnt <= kMaxGpu && ((unsigned)res.gpu_mask >> cnt) == 0u) {
+      int gl[kMaxGpu];
+      unpack_gl(n, gl);
+      body(n, gl);
+    }
+  }
+  return bound;
+}
+
+// Their tail, reached by every thread of the block: the pods in the API are every bound pod, candidate or not
+// (deschedule.go:21, :27).
+__device__ __forceinline__ void count_bound(const PlanArgs& a, int r, bool bound) {
+  const unsigned long long m = __ballot(bound);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(a.bound + r, (int)__popcll(m));
 }
 
 // grid (ceil(E_max / kEvalBlock), R), the replica's typical table staged in LDS: the candidate record
@@ -167,34 +198,25 @@ __global__ __launch_bounds__(kEvalBlock) void k_desched_eval(DsArgs a, const Typ
     out.pad = 0;
     const PodDev p = rp.ev[e];
     const ResultDev res = rp.res[e];
-    bound = !(p.flags & kPodDelete) && res.status == ST_OK && !a.gone[a.eoff[r] + e];
-    // the record is validated before it indexes anything: the node, then the mask against its GPUs
-    if (bound && res.node >= 0 && res.node < a.N && res.gpu_mask >= 0) {
-      const NodeV n = load_node(rp.nodes + res.node);
+    bound = eval_bound_node(a, rp, r, e, p, res, [&](const NodeV& n, const int (&gl)[kMaxGpu]) {
       const int cnt = n.gpu_cnt();
-      if (cnt <= kMaxGpu && ((unsigned)res.gpu_mask >> cnt) == 0u) {
-        int gl[kMaxGpu];
-        unpack_gl(n, gl);
-        const uint32_t tb = 1u << n.gpu_type();
-        const int cap = rp.cap[res.node];
-        out.node = res.node;
-        out.gpu_mask = res.gpu_mask;
-        if (rp.typed) {
-          out.f_node = frag_F<true>(n.cpu_left, gl, tb, s_tp, rp.ncpu, rp.nt);
-          out.ok = victim_eval<true>(n.cpu_left, gl, cnt, tb, cap, p.cpu_nz, p.milli, p.num, (unsigned)res.gpu_mask,
-                                     s_tp, rp.ncpu, rp.nt, &out.f_after) ? 1 : 0;
-        } else {
-          out.f_node = frag_F<false>(n.cpu_left, gl, tb, s_tp, rp.ncpu, rp.nt);
-          out.ok = victim_eval<false>(n.cpu_left, gl, cnt, tb, cap, p.cpu_nz, p.milli, p.num, (unsigned)res.gpu_mask,
-                                      s_tp, rp.ncpu, rp.nt, &out.f_after) ? 1 : 0;
-        }
+      const uint32_t tb = 1u << n.gpu_type();
+      const int cap = rp.cap[res.node];
+      out.node = res.node;
+      out.gpu_mask = res.gpu_mask;
+      if (rp.typed) {
+        out.f_node = frag_F<true>(n.cpu_left, gl, tb, s_tp, rp.ncpu, rp.nt);
+        out.ok = victim_eval<true>(n.cpu_left, gl, cnt, tb, cap, p.cpu_nz, p.milli, p.num, (unsigned)res.gpu_mask,
+                                   s_tp, rp.ncpu, rp.nt, &out.f_after) ? 1 : 0;
+      } else {
+        out.f_node = frag_F<false>(n.cpu_left, gl, tb, s_tp, rp.ncpu, rp.nt);
+        out.ok = victim_eval<false>(n.cpu_left, gl, cnt, tb, cap, p.cpu_nz, p.milli, p.num, (unsigned)res.gpu_mask,
+                                    s_tp, rp.ncpu, rp.nt, &out.f_after) ? 1 : 0;
       }
-    }
+    });
     a.eval[a.eoff[r] + e] = out;
   }
-  // the pods in the API: every bound pod, candidate or not (deschedule.go:21, :27)
-  const unsigned long long m = __ballot(bound);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(a.bound + r, (int)__popcll(m));
+  count_bound(a, r, bound);
 }
 
 // int64(frag_before - frag_after): fp64 subtraction, truncation toward zero (deschedule_utils.go:92).
@@ -244,7 +266,7 @@ __global__ __launch_bounds__(kSelBlock) void k_desched_select(DsArgs a) {
   const EvalRec* ev = a.eval + a.eoff[r];
   int32_t* plist = a.plist + a.eoff[r];
   ksim_victim* vict = a.vict + a.eoff[r];
-  uint8_t* base = a.tab ? a.tab + (size_t)r * sel_tab_stride(N) : s_dyn;
+  uint8_t* base = a.tab ? a.tab + (size_t)r * tab_stride(N, kSelNodeBytes) : s_dyn;
   unsigned long long* nkey = reinterpret_cast<unsigned long long*>(base);
   unsigned* nrank = reinterpret_cast<unsigned*>(base + (size_t)N * 8);
   int* nstart = reinterpret_cast<int*>(base + (size_t)N * 12);
@@ -394,21 +416,12 @@ static_assert(sizeof(ksim_cos_victim) == 32, "ksim_cos_victim layout");
 
 // per-node tables of k_cos_select: the least similarity's bits 8, sort key 8, its pod 4, node index 4
 constexpr int kCosNodeBytes = 24;
-KSIM_HD size_t cos_tab_stride(int N) { return ((size_t)N * kCosNodeBytes + 15) & ~(size_t)15; }
 
-struct CosArgs {
-  const ReplicaDev* reps;
-  const long long* eoff;   // [R + 1]
+struct CosArgs : PlanArgs {
   CosRec* rec;             // [Σ E]
-  const uint8_t* gone;     // [Σ E] k_desched_mark's
   ksim_cos_victim* vict;   // [Σ E]
-  int32_t* bound;          // [R]
-  const int32_t* budget;   // [R]
-  int32_t* n_vict;         // [R]
-  uint8_t* tab;            // [R][cos_tab_stride(N)] when the tables do not fit in LDS, else null
   long long cpu_bar;       // milliCpuBar: a node at or above it is skipped
   long long gpu_bar;       // milliGpuBar: some device of the node must have more than it left
-  int N;
 };
 
 // A pod is elected only with 0 <= similarity < 1 (deschedule_utils.go:34, victimPodSimilarity starts at 1).
@@ -429,24 +442,15 @@ __global__ __launch_bounds__(kEvalBlock) void k_cos_eval(CosArgs a) {
     out.gpu_mask = 0;
     const PodDev p = rp.ev[e];
     const ResultDev res = rp.res[e];
-    bound = !(p.flags & kPodDelete) && res.status == ST_OK && !a.gone[a.eoff[r] + e];
-    // the record is validated before it indexes anything: the node, then the mask against its GPUs
-    if (bound && res.node >= 0 && res.node < a.N && res.gpu_mask >= 0) {
-      const NodeV n = load_node(rp.nodes + res.node);
-      const int cnt = n.gpu_cnt();
-      if (cnt <= kMaxGpu && ((unsigned)res.gpu_mask >> cnt) == 0u) {
-        int gl[kMaxGpu];
-        unpack_gl(n, gl);
-        out.node = res.node;
-        out.gpu_mask = res.gpu_mask;
-        out.sim = cos_similarity(n.cpu_left, gl, cnt, rp.cap[res.node], p.cpu_nz, p.milli, p.num,
-                                 (unsigned)res.gpu_mask);
-      }
-    }
+    bound = eval_bound_node(a, rp, r, e, p, res, [&](const NodeV& n, const int (&gl)[kMaxGpu]) {
+      out.node = res.node;
+      out.gpu_mask = res.gpu_mask;
+      out.sim = cos_similarity(n.cpu_left, gl, n.gpu_cnt(), rp.cap[res.node], p.cpu_nz, p.milli, p.num,
+                               (unsigned)res.gpu_mask);
+    });
     a.rec[a.eoff[r] + e] = out;
   }
-  const unsigned long long m = __ballot(bound);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(a.bound + r, (int)__popcll(m));
+  count_bound(a, r, bound);
 }
 
 // One workgroup per replica.  The arg-min in two passes over the events (the 64-bit similarity and the event do
@@ -464,7 +468,7 @@ __global__ __launch_bounds__(kSelBlock) void k_cos_select(CosArgs a) {
   const int N = a.N, E = rp.n_events;
   const CosRec* rec = a.rec + a.eoff[r];
   ksim_cos_victim* vict = a.vict + a.eoff[r];
-  uint8_t* base = a.tab ? a.tab + (size_t)r * cos_tab_stride(N) : s_dyn;
+  uint8_t* base = a.tab ? a.tab + (size_t)r * tab_stride(N, kCosNodeBytes) : s_dyn;
   unsigned long long* nbits = reinterpret_cast<unsigned long long*>(base);
   unsigned long long* skey = reinterpret_cast<unsigned long long*>(base + (size_t)N * 8);
   unsigned* nev = reinterpret_cast<unsigned*>(base + (size_t)N * 16);

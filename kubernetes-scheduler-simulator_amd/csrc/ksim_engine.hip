@@ -1778,6 +1778,7 @@ __global__ __launch_bounds__(64) void k_reserve(ReplicaDev* reps, const TypDev* 
 
 #include "ksim_host.hpp"
 #include "ksim_report_host.hpp"
+#include "ksim_desched_host.hpp"
 
 // ---------------------------------------------------------------------------
 // Host engine object
@@ -1819,12 +1820,31 @@ struct HMemoState {  // k_hmemo (the keys in HBM)
   DevBuf<uint8_t> hist;  // the wide form with deletes: per-workgroup bind history
 };
 
+enum DsPlan { kDsNone, kDsFrag, kDsCos };
+struct DeschedState {  // the descheduling plan (desched_plan), made from the results and final node records of the
+                       // last completed run: an engine holds one, of one policy
+  DsPlan plan = kDsNone;
+  std::vector<long long> eoff;      // [R + 1] each replica's offset in the per-event buffers
+  std::vector<int32_t> budget, nv;  // [R]
+  DevBuf<long long> d_eoff;
+  DevBuf<uint8_t> gone;
+  DevBuf<int32_t> cnt;              // [3][R] bound pods, budget, victims
+  DevBuf<uint8_t> tab;              // the select kernel's per-node tables when they do not fit in LDS
+  DevBuf<ksim_ds::EvalRec> eval;    // frag policies: per-event records, candidate lists, victims
+  DevBuf<int32_t> plist;
+  DevBuf<ksim_victim> vict;
+  DevBuf<ksim_ds::CosRec> cos;      // cosSim: per-event records, victims
+  DevBuf<ksim_cos_victim> cvict;
+  DevEvent ev0, ev1;
+  double last_ms = 0;
+  void invalidate() { plan = kDsNone; }
+};
+
 // Every device resource is a member handle (ksim_host.hpp) that frees itself: a new buffer is one new member and nothing
 // else.  Declaration order carries meaning, since members go in reverse: the streams come first and so go last, after
 // every buffer and event used on them.  Before that the destructor sets the device, drains the side streams and then
 // the engine's (no dispatch, or a profiler's completion callback on it, may outlive its buffers, streams or graph),
 // destroys the graph and the communicator, and closes the peers' IPC-opened buffers.
-enum DsPlan { kDsNone, kDsFrag, kDsCos };  // the descheduling plan an engine holds
 struct ksim_engine {
   int device = 0;
   static constexpr int kSide = kSideStreams;
@@ -1957,24 +1977,8 @@ struct ksim_engine {
   std::vector<std::vector<unsigned long long>> go_state;
   DevBuf<unsigned long long> d_go;
   int64_t last_steps = 0;
-  // descheduling plan (ksim_engine_deschedule): made from the results and final node records of the last
-  // completed run; per-event buffers at each replica's offset ds_eoff[r]
   bool ran = false;      // a ksim_engine_run completed since the last set_nodes / set_typical / load_events
-  DsPlan ds_plan = kDsNone;  // which plan of that run is held: an engine holds one
-  DevBuf<ksim_ds::EvalRec> d_ds_eval;
-  DevBuf<uint8_t> d_ds_gone;
-  DevBuf<int32_t> d_ds_plist;
-  DevBuf<ksim_victim> d_ds_vict;
-  DevBuf<int32_t> d_ds_cnt;    // [3][R] bound pods, budget, victims
-  DevBuf<long long> d_ds_eoff;
-  DevBuf<uint8_t> d_ds_tab;    // k_desched_select's per-node tables when they do not fit in LDS
-  DevBuf<ksim_ds::CosRec> d_ds_cos;         // cosSim (ksim_engine_deschedule_cossim): per-event records,
-  DevBuf<ksim_cos_victim> d_ds_cvict;       // victims,
-  DevBuf<uint8_t> d_ds_ctab;                // and k_cos_select's per-node tables beyond LDS
-  std::vector<long long> ds_eoff;
-  std::vector<int32_t> ds_budget, ds_nv;
-  DevEvent ev_ds0, ev_ds1;
-  double last_ds_ms = 0;
+  DeschedState ds;       // the descheduling plan made from that run
   ~ksim_engine();
 };
 
@@ -2822,7 +2826,7 @@ int ksim_engine_set_nodes(ksim_engine* e, int replica, const ksim_node* nodes) {
   e->h_rec[replica] = h;
   e->mplan_dirty = true;  // k_hmemo's plan holds the distinct initial node states
   e->ran = false;
-  e->ds_plan = kDsNone;
+  e->ds.invalidate();
   e->total_gpus[replica] = gpus;
   KSIM_HIP(hipSetDevice(e->device));
   KSIM_HIP(hipMemcpyAsync(e->d_cap.p + (size_t)replica * e->N, cap.data(), sizeof(int32_t) * e->N, hipMemcpyHostToDevice,
@@ -2877,7 +2881,7 @@ int ksim_engine_set_typical(ksim_engine* e, int replica, const ksim_typical* tp,
   e->h_tp[replica] = h;
   e->mplan_dirty = true;  // k_hmemo's plan holds per-model views of the table
   e->ran = false;
-  e->ds_plan = kDsNone;
+  e->ds.invalidate();
   int rc = upload_reps(e);
   if (rc) return rc;
   KSIM_HIP(hipStreamSynchronize(e->stream));
@@ -3113,7 +3117,7 @@ int ksim_engine_load_events(ksim_engine* e, int replica, const ksim_pod* events,
   if (e) e->mplan_dirty = true;
   if (!e || replica < 0 || replica >= e->R || n < 0 || (n > 0 && !events)) return KSIM_EINVAL;
   e->ran = false;
-  e->ds_plan = kDsNone;
+  e->ds.invalidate();
   std::vector<PodDev> h(n);
   std::vector<char> gone(std::max(n, 1), 0);  // creations already deleted (the reference deletes a pod once)
   for (int i = 0; i < n; ++i) {
@@ -3822,7 +3826,7 @@ int ksim_engine_run(ksim_engine* e) {
   e->report_done = false;
   e->rep_ready = false;
   e->ran = false;
-  e->ds_plan = kDsNone;
+  e->ds.invalidate();
   e->grp_rev_used = 0;
   e->tev_used = 0u;  // KSIM_GROUP_TIMES: only run_persistent's concurrent groups record side-stream ends
   e->last_launches = 0;
@@ -4616,195 +4620,139 @@ int ksim_engine_get_nodes(ksim_engine* e, int replica, ksim_node* out) {
   return KSIM_OK;
 }
 
-// The descheduling plan of every replica from the last run's results and final node records
-// (ksim_desched.hpp): mark, evaluate, the budgets on the host from the bound-pod counts, select.
+}  // extern "C"
+
+// The descheduling plan of every replica from the last run's results and final node records (ksim_desched.hpp),
+// for every policy: mark, evaluate, the budgets on the host from the bound-pod counts (ksim_desched_host.hpp),
+// select.  The policy supplies the tag of its plan, the bytes per node of its select kernel's tables, its arguments
+// `a` with its own fields set, `ensure(tot, a)` for its per-event and victim buffers of tot elements and their
+// pointers in a, its eval kernel with what that takes after a, and its select kernel.
+template <class Args, class Ensure, class... Extra>
+static int desched_plan(ksim_engine* e, double ratio, DsPlan tag, int node_bytes, Args a, Ensure ensure,
+                        void (*eval)(Args, Extra...), void (*select)(Args), Extra... extra) {
+  if (e->shard_world > 0) return KSIM_ENOTSUP;
+  if (!e->ran) return KSIM_ESTATE;
+  DeschedState& ds = e->ds;
+  ds.invalidate();
+  KSIM_HIP(hipSetDevice(e->device));
+  const int R = e->R;
+  const int max_ev = ksim_ds_host::event_offsets(e->n_events.data(), R, ds.eoff);
+  const size_t tot = (size_t)ds.eoff[R];
+  int rc = ensure(tot, a);
+  if (!rc) rc = ds.gone.ensure(tot);
+  if (!rc) rc = ds.cnt.ensure((size_t)3 * R);
+  if (!rc) rc = ds.d_eoff.upload(ds.eoff, e->stream);
+  const size_t tab = (size_t)e->N * node_bytes;
+  const bool in_lds = tab <= (size_t)ksim_ds::kSelLdsBytes;
+  if (!rc && !in_lds) rc = ds.tab.ensure(ksim_ds::tab_stride(e->N, node_bytes) * R);
+  if (rc) return rc;
+  if (ds.ev0.ensure() || ds.ev1.ensure()) return KSIM_EHIP;
+  a.reps = e->d_reps.p;
+  a.eoff = ds.d_eoff.p;
+  a.gone = ds.gone.p;
+  a.bound = ds.cnt.p;
+  a.budget = ds.cnt.p + R;
+  a.n_vict = ds.cnt.p + 2 * R;
+  a.tab = in_lds ? nullptr : ds.tab.p;
+  a.N = e->N;
+  KSIM_HIP(hipEventRecord(ds.ev0, e->stream));
+  if (tot) KSIM_HIP(hipMemsetAsync(ds.gone.p, 0, tot, e->stream));
+  KSIM_HIP(hipMemsetAsync(ds.cnt.p, 0, sizeof(int32_t) * 3 * R, e->stream));
+  if (max_ev > 0) {
+    const dim3 grid((unsigned)((max_ev + ksim_ds::kEvalBlock - 1) / ksim_ds::kEvalBlock), (unsigned)R);
+    hipLaunchKernelGGL(ksim_ds::k_desched_mark, grid, dim3(ksim_ds::kEvalBlock), 0, e->stream, (ksim_ds::PlanArgs)a);
+    KSIM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(eval, grid, dim3(ksim_ds::kEvalBlock), 0, e->stream, a, extra...);
+    KSIM_HIP(hipGetLastError());
+  }
+  std::vector<int32_t> bound((size_t)R, 0);
+  KSIM_HIP(hipMemcpyAsync(bound.data(), a.bound, sizeof(int32_t) * R, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipStreamSynchronize(e->stream));
+  ds.budget.assign((size_t)R, 0);
+  for (int r = 0; r < R; ++r) ds.budget[r] = ksim_ds_host::budget(ratio, bound[r]);
+  KSIM_HIP(hipMemcpyAsync(ds.cnt.p + R, ds.budget.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(select, dim3((unsigned)R), dim3(ksim_ds::kSelBlock), in_lds ? tab : (size_t)0, e->stream, a);
+  KSIM_HIP(hipGetLastError());
+  ds.nv.assign((size_t)R, 0);
+  KSIM_HIP(hipMemcpyAsync(ds.nv.data(), a.n_vict, sizeof(int32_t) * R, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipEventRecord(ds.ev1, e->stream));
+  KSIM_HIP(hipStreamSynchronize(e->stream));
+  float ms = 0;
+  KSIM_HIP(hipEventElapsedTime(&ms, ds.ev0, ds.ev1));
+  ds.last_ms = ms;
+  ds.plan = tag;
+  return KSIM_OK;
+}
+
+// A replica's victims of the plan kTag, which the engine must hold, from that policy's victim buffer.
+template <DsPlan kTag, class V>
+static int plan_victims(ksim_engine* e, DevBuf<V> DeschedState::*vict, int replica, V* out, int cap, int* n_out,
+                        int* budget_out) {
+  if (!e || replica < 0 || replica >= e->R || cap < 0 || !n_out) return KSIM_EINVAL;
+  const DeschedState& ds = e->ds;
+  if (ds.plan != kTag) return KSIM_ESTATE;
+  const int n = ds.nv[replica];
+  *n_out = n;
+  if (budget_out) *budget_out = ds.budget[replica];
+  if (cap < n) return KSIM_ERANGE;
+  if (n == 0) return KSIM_OK;
+  if (!out) return KSIM_EINVAL;
+  KSIM_HIP(hipSetDevice(e->device));
+  KSIM_HIP(hipMemcpyAsync(out, (ds.*vict).p + ds.eoff[replica], sizeof(V) * n, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipStreamSynchronize(e->stream));
+  return KSIM_OK;
+}
+
+extern "C" {
+
 int ksim_engine_deschedule(ksim_engine* e, int policy, double ratio) {
   if (check_gfx950(e ? e->device : 0)) return KSIM_ENODEV;
   if (!e) return KSIM_EINVAL;
   if (policy != KSIM_DESCHED_FRAG_ONE_POD && policy != KSIM_DESCHED_FRAG_MULTI_POD) return KSIM_EINVAL;
   if (!(ratio >= 0.0)) return KSIM_EINVAL;  // negative or NaN
-  if (e->shard_world > 0) return KSIM_ENOTSUP;
-  if (!e->ran) return KSIM_ESTATE;
-  e->ds_plan = kDsNone;
-  KSIM_HIP(hipSetDevice(e->device));
-  const int R = e->R;
-  int max_ev = 0;
-  e->ds_eoff.assign((size_t)R + 1, 0);
-  for (int r = 0; r < R; ++r) {
-    e->ds_eoff[r + 1] = e->ds_eoff[r] + e->n_events[r];
-    max_ev = std::max(max_ev, e->n_events[r]);
-  }
-  const size_t tot = (size_t)e->ds_eoff[R];
-  int rc = e->d_ds_eval.ensure(tot);
-  if (!rc) rc = e->d_ds_gone.ensure(tot);
-  if (!rc) rc = e->d_ds_plist.ensure(tot);
-  if (!rc) rc = e->d_ds_vict.ensure(tot);
-  if (!rc) rc = e->d_ds_cnt.ensure((size_t)3 * R);
-  if (!rc) rc = e->d_ds_eoff.upload(e->ds_eoff, e->stream);
-  const size_t tab = (size_t)e->N * ksim_ds::kSelNodeBytes;
-  const bool in_lds = tab <= (size_t)ksim_ds::kSelLdsBytes;
-  if (!rc && !in_lds) rc = e->d_ds_tab.ensure(ksim_ds::sel_tab_stride(e->N) * R);
-  if (rc) return rc;
-  if (e->ev_ds0.ensure() || e->ev_ds1.ensure()) return KSIM_EHIP;
-  ksim_ds::DsArgs a;
-  a.reps = e->d_reps.p;
-  a.eoff = e->d_ds_eoff.p;
-  a.eval = e->d_ds_eval.p;
-  a.gone = e->d_ds_gone.p;
-  a.plist = e->d_ds_plist.p;
-  a.vict = e->d_ds_vict.p;
-  a.bound = e->d_ds_cnt.p;
-  a.budget = e->d_ds_cnt.p + R;
-  a.n_vict = e->d_ds_cnt.p + 2 * R;
-  a.tab = in_lds ? nullptr : e->d_ds_tab.p;
-  a.N = e->N;
+  ksim_ds::DsArgs a = {};
   a.policy = policy;
-  KSIM_HIP(hipEventRecord(e->ev_ds0, e->stream));
-  if (tot) KSIM_HIP(hipMemsetAsync(e->d_ds_gone.p, 0, tot, e->stream));
-  KSIM_HIP(hipMemsetAsync(e->d_ds_cnt.p, 0, sizeof(int32_t) * 3 * R, e->stream));
-  if (max_ev > 0) {
-    const dim3 grid((unsigned)((max_ev + ksim_ds::kEvalBlock - 1) / ksim_ds::kEvalBlock), (unsigned)R);
-    hipLaunchKernelGGL(ksim_ds::k_desched_mark, grid, dim3(ksim_ds::kEvalBlock), 0, e->stream, a);
-    KSIM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ksim_ds::k_desched_eval, grid, dim3(ksim_ds::kEvalBlock), 0, e->stream, a, (const TypDev*)e->d_tp.p);
-    KSIM_HIP(hipGetLastError());
-  }
-  std::vector<int32_t> bound((size_t)R, 0);
-  KSIM_HIP(hipMemcpyAsync(bound.data(), a.bound, sizeof(int32_t) * R, hipMemcpyDeviceToHost, e->stream));
-  KSIM_HIP(hipStreamSynchronize(e->stream));
-  // deschedule.go:27 int(math.Ceil(ratio * float64(len(podMap)))); never more than the pods there are
-  e->ds_budget.assign((size_t)R, 0);
-  for (int r = 0; r < R; ++r)
-    e->ds_budget[r] = (int32_t)std::min(std::ceil(ratio * (double)bound[r]), (double)bound[r]);
-  KSIM_HIP(hipMemcpyAsync(e->d_ds_cnt.p + R, e->ds_budget.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, e->stream));
-  hipLaunchKernelGGL(ksim_ds::k_desched_select, dim3((unsigned)R), dim3(ksim_ds::kSelBlock), in_lds ? tab : (size_t)0,
-                     e->stream, a);
-  KSIM_HIP(hipGetLastError());
-  e->ds_nv.assign((size_t)R, 0);
-  KSIM_HIP(hipMemcpyAsync(e->ds_nv.data(), a.n_vict, sizeof(int32_t) * R, hipMemcpyDeviceToHost, e->stream));
-  KSIM_HIP(hipEventRecord(e->ev_ds1, e->stream));
-  KSIM_HIP(hipStreamSynchronize(e->stream));
-  float ms = 0;
-  KSIM_HIP(hipEventElapsedTime(&ms, e->ev_ds0, e->ev_ds1));
-  e->last_ds_ms = ms;
-  e->ds_plan = kDsFrag;
-  return KSIM_OK;
+  DeschedState& ds = e->ds;
+  const auto ensure = [&ds](size_t tot, ksim_ds::DsArgs& a) {
+    int rc = ds.eval.ensure(tot);
+    if (!rc) rc = ds.plist.ensure(tot);
+    if (!rc) rc = ds.vict.ensure(tot);
+    a.eval = ds.eval.p, a.plist = ds.plist.p, a.vict = ds.vict.p;
+    return rc;
+  };
+  return desched_plan(e, ratio, kDsFrag, ksim_ds::kSelNodeBytes, a, ensure, ksim_ds::k_desched_eval,
+                      ksim_ds::k_desched_select, (const TypDev*)e->d_tp.p);
 }
 
 int ksim_engine_get_victims(ksim_engine* e, int replica, ksim_victim* out, int cap, int* n_out, int* budget_out) {
-  if (!e || replica < 0 || replica >= e->R || cap < 0 || !n_out) return KSIM_EINVAL;
-  if (e->ds_plan != kDsFrag) return KSIM_ESTATE;
-  const int n = e->ds_nv[replica];
-  *n_out = n;
-  if (budget_out) *budget_out = e->ds_budget[replica];
-  if (cap < n) return KSIM_ERANGE;
-  if (n == 0) return KSIM_OK;
-  if (!out) return KSIM_EINVAL;
-  KSIM_HIP(hipSetDevice(e->device));
-  KSIM_HIP(hipMemcpyAsync(out, e->d_ds_vict.p + e->ds_eoff[replica], sizeof(ksim_victim) * n, hipMemcpyDeviceToHost,
-                          e->stream));
-  KSIM_HIP(hipStreamSynchronize(e->stream));
-  return KSIM_OK;
+  return plan_victims<kDsFrag>(e, &DeschedState::vict, replica, out, cap, n_out, budget_out);
 }
 
-// The cosSim plan of every replica (ksim_desched.hpp): mark, evaluate, the budgets on the host from the bound-pod
-// counts, select.
 int ksim_engine_deschedule_cossim(ksim_engine* e, double ratio, int64_t cpu_bar_milli, int64_t gpu_bar_milli) {
   if (check_gfx950(e ? e->device : 0)) return KSIM_ENODEV;
   if (!e) return KSIM_EINVAL;
   if (!(ratio >= 0.0) || cpu_bar_milli < 0 || gpu_bar_milli < 0) return KSIM_EINVAL;
-  if (e->shard_world > 0) return KSIM_ENOTSUP;
-  if (!e->ran) return KSIM_ESTATE;
-  e->ds_plan = kDsNone;
-  KSIM_HIP(hipSetDevice(e->device));
-  const int R = e->R;
-  int max_ev = 0;
-  e->ds_eoff.assign((size_t)R + 1, 0);
-  for (int r = 0; r < R; ++r) {
-    e->ds_eoff[r + 1] = e->ds_eoff[r] + e->n_events[r];
-    max_ev = std::max(max_ev, e->n_events[r]);
-  }
-  const size_t tot = (size_t)e->ds_eoff[R];
-  int rc = e->d_ds_cos.ensure(tot);
-  if (!rc) rc = e->d_ds_gone.ensure(tot);
-  if (!rc) rc = e->d_ds_cvict.ensure(tot);
-  if (!rc) rc = e->d_ds_cnt.ensure((size_t)3 * R);
-  if (!rc) rc = e->d_ds_eoff.upload(e->ds_eoff, e->stream);
-  const size_t tab = (size_t)e->N * ksim_ds::kCosNodeBytes;
-  const bool in_lds = tab <= (size_t)ksim_ds::kSelLdsBytes;
-  if (!rc && !in_lds) rc = e->d_ds_ctab.ensure(ksim_ds::cos_tab_stride(e->N) * R);
-  if (rc) return rc;
-  if (e->ev_ds0.ensure() || e->ev_ds1.ensure()) return KSIM_EHIP;
-  ksim_ds::DsArgs m = {};  // k_desched_mark reads reps, eoff and gone
-  m.reps = e->d_reps.p;
-  m.eoff = e->d_ds_eoff.p;
-  m.gone = e->d_ds_gone.p;
-  m.N = e->N;
-  ksim_ds::CosArgs a;
-  a.reps = e->d_reps.p;
-  a.eoff = e->d_ds_eoff.p;
-  a.rec = e->d_ds_cos.p;
-  a.gone = e->d_ds_gone.p;
-  a.vict = e->d_ds_cvict.p;
-  a.bound = e->d_ds_cnt.p;
-  a.budget = e->d_ds_cnt.p + R;
-  a.n_vict = e->d_ds_cnt.p + 2 * R;
-  a.tab = in_lds ? nullptr : e->d_ds_ctab.p;
+  ksim_ds::CosArgs a = {};
   a.cpu_bar = (long long)cpu_bar_milli;
   a.gpu_bar = (long long)gpu_bar_milli;
-  a.N = e->N;
-  KSIM_HIP(hipEventRecord(e->ev_ds0, e->stream));
-  if (tot) KSIM_HIP(hipMemsetAsync(e->d_ds_gone.p, 0, tot, e->stream));
-  KSIM_HIP(hipMemsetAsync(e->d_ds_cnt.p, 0, sizeof(int32_t) * 3 * R, e->stream));
-  if (max_ev > 0) {
-    const dim3 grid((unsigned)((max_ev + ksim_ds::kEvalBlock - 1) / ksim_ds::kEvalBlock), (unsigned)R);
-    hipLaunchKernelGGL(ksim_ds::k_desched_mark, grid, dim3(ksim_ds::kEvalBlock), 0, e->stream, m);
-    KSIM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ksim_ds::k_cos_eval, grid, dim3(ksim_ds::kEvalBlock), 0, e->stream, a);
-    KSIM_HIP(hipGetLastError());
-  }
-  std::vector<int32_t> bound((size_t)R, 0);
-  KSIM_HIP(hipMemcpyAsync(bound.data(), a.bound, sizeof(int32_t) * R, hipMemcpyDeviceToHost, e->stream));
-  KSIM_HIP(hipStreamSynchronize(e->stream));
-  // deschedule.go:27 int(math.Ceil(ratio * float64(len(podMap)))); never more than the pods there are
-  e->ds_budget.assign((size_t)R, 0);
-  for (int r = 0; r < R; ++r)
-    e->ds_budget[r] = (int32_t)std::min(std::ceil(ratio * (double)bound[r]), (double)bound[r]);
-  KSIM_HIP(hipMemcpyAsync(e->d_ds_cnt.p + R, e->ds_budget.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, e->stream));
-  hipLaunchKernelGGL(ksim_ds::k_cos_select, dim3((unsigned)R), dim3(ksim_ds::kSelBlock), in_lds ? tab : (size_t)0,
-                     e->stream, a);
-  KSIM_HIP(hipGetLastError());
-  e->ds_nv.assign((size_t)R, 0);
-  KSIM_HIP(hipMemcpyAsync(e->ds_nv.data(), a.n_vict, sizeof(int32_t) * R, hipMemcpyDeviceToHost, e->stream));
-  KSIM_HIP(hipEventRecord(e->ev_ds1, e->stream));
-  KSIM_HIP(hipStreamSynchronize(e->stream));
-  float ms = 0;
-  KSIM_HIP(hipEventElapsedTime(&ms, e->ev_ds0, e->ev_ds1));
-  e->last_ds_ms = ms;
-  e->ds_plan = kDsCos;
-  return KSIM_OK;
+  DeschedState& ds = e->ds;
+  const auto ensure = [&ds](size_t tot, ksim_ds::CosArgs& a) {
+    int rc = ds.cos.ensure(tot);
+    if (!rc) rc = ds.cvict.ensure(tot);
+    a.rec = ds.cos.p, a.vict = ds.cvict.p;
+    return rc;
+  };
+  return desched_plan(e, ratio, kDsCos, ksim_ds::kCosNodeBytes, a, ensure, ksim_ds::k_cos_eval, ksim_ds::k_cos_select);
 }
 
 int ksim_engine_get_cos_victims(ksim_engine* e, int replica, ksim_cos_victim* out, int cap, int* n_out,
                                 int* budget_out) {
-  if (!e || replica < 0 || replica >= e->R || cap < 0 || !n_out) return KSIM_EINVAL;
-  if (e->ds_plan != kDsCos) return KSIM_ESTATE;
-  const int n = e->ds_nv[replica];
-  *n_out = n;
-  if (budget_out) *budget_out = e->ds_budget[replica];
-  if (cap < n) return KSIM_ERANGE;
-  if (n == 0) return KSIM_OK;
-  if (!out) return KSIM_EINVAL;
-  KSIM_HIP(hipSetDevice(e->device));
-  KSIM_HIP(hipMemcpyAsync(out, e->d_ds_cvict.p + e->ds_eoff[replica], sizeof(ksim_cos_victim) * n,
-                          hipMemcpyDeviceToHost, e->stream));
-  KSIM_HIP(hipStreamSynchronize(e->stream));
-  return KSIM_OK;
+  return plan_victims<kDsCos>(e, &DeschedState::cvict, replica, out, cap, n_out, budget_out);
 }
 
 int ksim_engine_last_deschedule_ms(ksim_engine* e, double* ms) {
   if (!e || !ms) return KSIM_EINVAL;
-  *ms = e->last_ds_ms;
+  *ms = e->ds.last_ms;
   return KSIM_OK;
 }
 

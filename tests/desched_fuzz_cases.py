@@ -23,6 +23,8 @@ COS_STRIDE_N = [1, 2, 3, 64, 65, 255, 256, 257, 512, 513]
 COS_SWITCH_N = [2560, 2561]
 FRAG_STRIDE_N = [1, 63, 64, 65, 255, 256, 257]
 FRAG_SWITCH_N = [3072, 3073]
+# one engine planning every policy in turn over one buffer of tables in HBM: past both switches, the usual stream
+SHARED_TAB_N, SHARED_TAB_PODS = 3073, 700
 
 FRAG_MILLI = [600, 700, 800, 900, 550, 650, 750]
 
@@ -58,10 +60,11 @@ def flat_cos(n):
     return cos_cases._case(nodes, cos_cases.TYP, pods)
 
 
-def flat_frag(n):
+def flat_frag(n, n_pods=None):
     """n one-GPU nodes of 4000 milli-CPU with scrambled names and n pods of 2500 milli-CPU: one pod a node, and
     the 1500 milli-CPU left host neither typical pod, so F(node) is the GPU milli left (seven values) and giving
-    the pod back makes it 0.  Every node has a frag victim; the priorities tie over a seventh of the nodes."""
+    the pod back makes it 0.  Every node has a frag victim; the priorities tie over a seventh of the nodes.
+    n_pods < n: only that many nodes get a pod (and a frag victim, and under wide bars a cosSim one)."""
     nodes = [(name, 0, 1, 4000, 1000) for name in scrambled_names(n)]
-    pods = [dict(cpu=2500, milli=FRAG_MILLI[i % 7], num=1, model=None) for i in range(n)]
+    pods = [dict(cpu=2500, milli=FRAG_MILLI[i % 7], num=1, model=None) for i in range(n if n_pods is None else n_pods)]
     return cos_cases._case(nodes, cos_cases.TYP, pods)

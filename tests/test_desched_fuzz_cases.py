@@ -169,3 +169,16 @@ def test_flat_frag_every_node_has_a_victim(n):
         half = ref.plan(c["onodes"], c["otyp"], c["oev"], res, state, ref.ONE_POD, 0.5)[0]
         assert sorted({v["frag_before"] for v in half}) == [300.0, 350.0, 400.0, 450.0]
         assert half[-1]["frag_before"] == victims[len(half)]["frag_before"]  # the name rank decides who is in
+
+
+def test_shared_table_case_has_victims_of_every_policy_up_to_the_last_nodes():
+    n, m = fz.SHARED_TAB_N, fz.SHARED_TAB_PODS
+    assert n * 24 > n * 20 > 60 * 1024  # both policies' tables are in HBM, cosSim's the larger
+    c = fz.flat_frag(n, m)
+    res, state = oracle_run(c, ("shared_tab", n, m), "FGD")
+    assert len({r[0] for r in res}) == m  # one pod a node
+    for victims in (ref.plan(c["onodes"], c["otyp"], c["oev"], res, state, ref.MULTI_POD, 1.0)[0],
+                    cos.plan(c["onodes"], c["oev"], res, state, 1.0, *WIDE)[0],
+                    ref.plan(c["onodes"], c["otyp"], c["oev"], res, state, ref.ONE_POD, 1.0)[0]):
+        assert len(victims) == m and max(v["node"] for v in victims) > n - 64
+

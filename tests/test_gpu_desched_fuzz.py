@@ -12,7 +12,10 @@ reaches its target):
   whole sorted order is written out and compared;
 - both sides of the LDS / HBM switch of the two select kernels (2560 / 2561 and 3072 / 3073 nodes), with every
   node queued or sorted;
-- a second plan on the ragged streams that ksim.desched.run extended.
+- a second plan on the ragged streams that ksim.desched.run extended;
+- one engine of 3073 nodes planning fragMultiPod, cosSim and fragOnePod in turn: the three share one buffer for
+  the tables in HBM, which cosSim needs larger (24 B a node) than the frag policies (20 B);
+- ratio = +inf with an empty replica: the budget is defined (0 there, every bound pod elsewhere).
 Every test needs a gfx950 device.
 """
 import ctypes as C
@@ -165,6 +168,51 @@ def test_desched_select_lds_hbm_switch(n):
     # 3072 nodes: the largest in-LDS launch; 3073: every node queued and popped over tables in HBM
     assert (n * 20 <= 60 * 1024) == (n == 3072)
     check_flat_frag(n)
+
+
+def test_every_policy_in_turn_over_one_table_buffer():
+    n, m = fz.SHARED_TAB_N, fz.SHARED_TAB_PODS
+    assert n * 24 > n * 20 > 60 * 1024
+    case, key = fz.flat_frag(n, m), ("shared_tab", n, m)
+    eng = make_engine(case)
+    eng.run()
+    assert eng.results(0) == oracle_run(case, key, "FGD")[0]
+    # the table buffer is first made for 20 B a node, grows for cosSim, and is then used again at 20 B a node
+    eng.deschedule(ref.MULTI_POD, 1.0)
+    got = frag.got_plan(eng, 0)
+    assert got == frag.want_plan(case, key, "FGD", ref.MULTI_POD, 1.0) and len(got[0]) == got[1] == m
+    for ratio in (1.0, 0.3):
+        eng.deschedule_cossim(ratio, *WIDE)
+        got = cosm.got_plan(eng, 0)
+        assert got == cosm.want_plan(case, key, "FGD", ratio, WIDE) and len(got[0]) == got[1] > 0
+    for ratio in (1.0, 0.3):
+        eng.deschedule(ref.ONE_POD, ratio)
+        got = frag.got_plan(eng, 0)
+        assert got == frag.want_plan(case, key, "FGD", ref.ONE_POD, ratio) and len(got[0]) == got[1] > 0
+    eng.close()
+
+
+def test_infinite_ratio_with_an_empty_replica():
+    # inf * 0 bound pods is a NaN: the budget must not be made from it (the reference's formula raises at inf)
+    reps = [(fz.from_fuzz(20 + r, 150, 580, 0.2, n_events=n), "FGD") for r, n in enumerate([257, 0])]
+    eng = engine_of(reps)
+    eng.run()
+    L = ksim.lib()
+    inf = float("inf")
+    full = frag.want_plan(reps[0][0], ("ragged", 0, 257), "FGD", ref.MULTI_POD, 1.0)
+    assert full[1] > 0
+    for policy in POLICIES:
+        assert L.ksim_engine_deschedule(eng.h, ksim.DESCHED_POLICY[policy], inf) == ksim.KSIM_OK
+        assert frag.got_plan(eng, 1) == ([], 0)
+        n, b = C.c_int(-1), C.c_int(-1)
+        assert L.ksim_engine_get_victims(eng.h, 1, None, 0, C.byref(n), C.byref(b)) == ksim.KSIM_OK
+        assert (n.value, b.value) == (0, 0)
+        # every bound pod of the other replica: the plan of ratio 1
+        assert frag.got_plan(eng, 0) == frag.want_plan(reps[0][0], ("ragged", 0, 257), "FGD", policy, 1.0)
+    assert L.ksim_engine_deschedule_cossim(eng.h, inf, *WIDE) == ksim.KSIM_OK
+    assert cosm.got_plan(eng, 1) == ([], 0)
+    assert cosm.got_plan(eng, 0) == cosm.want_plan(reps[0][0], ("ragged", 0, 257), "FGD", 1.0, WIDE)
+    eng.close()
 
 
 def test_second_round_on_extended_streams():
