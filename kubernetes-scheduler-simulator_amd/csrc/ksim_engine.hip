@@ -1779,6 +1779,7 @@ __global__ __launch_bounds__(64) void k_reserve(ReplicaDev* reps, const TypDev* 
 #include "ksim_host.hpp"
 #include "ksim_report_host.hpp"
 #include "ksim_desched_host.hpp"
+#include "ksim_run_host.hpp"
 
 // ---------------------------------------------------------------------------
 // Host engine object
@@ -1840,11 +1841,55 @@ struct DeschedState {  // the descheduling plan (desched_plan), made from the re
   void invalidate() { plan = kDsNone; }
 };
 
+static hipError_t destroy_comm(ncclComm_t c);  // through the dlopen'd RCCL
+using ShardComm = DevHandle<ncclComm_t, destroy_comm>;
+
+struct ShardState {  // a node-sharded cluster's shard (ksim_engine_set_shard): its place, its transport and what that holds
+  int world = 0;     // 0: not sharded
+  int rank = 0, node_off = 0, n_global = 0;
+  ShardTransport transport = ShardTransport::none;
+  // the per-step exchange records (the k_step paths of every transport but peer)
+  DevBuf<unsigned long long> d_send;  // this shard's record {best, nfeas, err, lo|hi}
+  DevBuf<unsigned long long> d_recv;  // [world][4] gathered records
+  ShardComm comm;                     // rccl (declared after the records it gathers: destroyed before they are freed)
+  ksim_shard_exchange_fn xfn = nullptr;  // host (ksim_engine_set_shard_exchange)
+  void* xuser = nullptr;
+  std::vector<uint64_t> h_send, h_recv;  // its staging records
+  // peer, one shard per process (ksim_shard_peer_handle / ksim_engine_set_shard_peers): this shard's exchange buffer
+  // (uncached device memory, exported by IPC), the handle exported (exports differ per call), the peers' buffers
+  // mapped here (closed before the own buffer is freed), the run epoch
+  DevBuf<unsigned long long> d_pgran;
+  std::vector<uint8_t> pgran_handle;
+  PeerMap peers;
+  int peer_epoch = 0;
+  // What an in-process group (ksim_shard_group_run) keeps: on engine 0 of the group only, empty on every other engine.
+  struct Group {
+    DevBuf<unsigned long long*> d_ptrs;     // k_step path: the shards' send / recv pointer tables
+    DevBuf<unsigned long long> d_ggran;     // k_hmemo_group: exchange granules
+    DevBuf<ksim_hmemo::HMemoArgs> d_hgargs; // its per-shard arguments
+    DevBuf<unsigned long long> d_rgran;     // k_replay group: exchange granules
+    DevBuf<ReplicaDev> d_rgreps;            // its shards' replicas, and their list
+    DevBuf<int> d_rglist;
+    DevBuf<RepAcc> d_rmerge;                // the merged report records (k_report_merge)
+    int rmerge_n = -1;  // events they hold (-1: no group run with the report on since the events were loaded)
+  } group;
+
+  // the entry points decide through these (ksim_run_host.hpp)
+  bool on() const { return shard_on(transport); }
+  bool runs_peer() const { return ::runs_peer(transport); }
+  bool exchanges_on_host() const { return ::exchanges_on_host(transport); }
+  bool exchanges_by_rccl() const { return ::exchanges_by_rccl(transport); }
+  bool needs_group_run() const { return ::needs_group_run(transport, world); }
+  bool takes_exchange_fn() const { return ::takes_exchange_fn(transport); }
+  bool in_process() const { return ::in_process(transport, xfn != nullptr); }
+  bool can_map_peers() const { return ::can_map_peers(transport, d_pgran.p && !pgran_handle.empty()); }
+};
+
 // Every device resource is a member handle (ksim_host.hpp) that frees itself: a new buffer is one new member and nothing
 // else.  Declaration order carries meaning, since members go in reverse: the streams come first and so go last, after
-// every buffer and event used on them.  Before that the destructor sets the device, drains the side streams and then
-// the engine's (no dispatch, or a profiler's completion callback on it, may outlive its buffers, streams or graph),
-// destroys the graph and the communicator, and closes the peers' IPC-opened buffers.
+// every buffer and event used on them, the communicator and the peers' mapped buffers (ShardState) included.  Before
+// that the destructor sets the device, drains the side streams and then the engine's (no dispatch, or a profiler's
+// completion callback on it, may outlive its buffers, streams or graph) and destroys the graph.
 struct ksim_engine {
   int device = 0;
   static constexpr int kSide = kSideStreams;
@@ -1861,7 +1906,6 @@ struct ksim_engine {
   DevBuf<int> d_fail;
   DevBuf<int> d_replist;              // replicas ordered by policy (k_replay groups)
   DevBuf<unsigned long long> d_prof;  // KSIM_PROFILE=1: k_replay phase timers
-  int last_K = 0;
   DevBuf<NodeRec> d_nodes;
   DevBuf<NodeRec> d_nodes_init;  // cluster state given to set_nodes (run() restarts from it)
   DevBuf<uint16_t> d_tags;  // per replica: N*16 u16 tags, then N int rank->index
@@ -1902,17 +1946,11 @@ struct ksim_engine {
   DevEvent ev_ovl;    // the queue's tickets zeroed (the report's stream waits on it)
   DevBuf<double> d_th;       // FGD score steps (build_score_thresholds), null if unusable
   std::vector<int> wgs_hint;    // per replica: workgroups asked by ksim_engine_set_replica_wgs (0: the engine's choice)
-  int last_memo = 0;
-  int last_hmemo = 0;
-  int last_rgo = 0;  // replicas the last run replayed on k_random_go
-  int last_scan1 = 0;  // replicas the last run replayed on k_scan1
-  int last_launches = 0, last_streams = 0;  // replay launches of the last run, side streams they ran on (0: none)
   std::vector<DevEvent> grp_rev;  // concurrent groups' report kernels: a timing event pair per group
   int grp_rev_used = 0;             // pairs recorded by the last run
   int scan1 = 2;       // single-workgroup cheap-policy groups on k_scan1, node records in VGPRs where they fit
                        // (KSIM_VARIANT scan1=1: records in LDS; 0: k_replay)
   std::vector<std::vector<NodeRec>> h_rec;  // the records set_nodes gave each replica (k_hmemo's initial states)
-  bool last_step_path = false;  // the last run went through k_step (run_mode 1 or a PWR replica)
   std::vector<int> nt;
   GraphExec graph;
   int graph_R = -1;
@@ -1924,10 +1962,7 @@ struct ksim_engine {
   DevEvent ev0, ev1, ev_mid;
   MappedFlags started;  // residency gate: host-mapped flags, one per FGD workgroup
   int gate_epoch = 0;
-  int last_ovl = 0;           // replicas the last run's overlapped report took (k_report_overlap)
-  int last_gate = 0;          // the last run's residency gate: 0 none, 1 opened, -1 given up at its bound (stderr note)
   long long gate_timeouts = 0;  // gates given up at their bound, over the engine's life
-  std::string last_kernels;    // the replay kernels the last run launched, '+'-joined in launch order
   DevEvent side_ev[kSide];
   DevEvent ev_fork;
   bool report_done = false;
@@ -1936,8 +1971,6 @@ struct ksim_engine {
   DevEvent tev_fork;
   DevEvent tev_side[kSide];
   unsigned tev_used = 0u;
-  int last_pf_memo = 0;      // PWR+FGD memo class stride of the last k_replay<PWR+FGD> launch (0: none)
-  double last_ms = 0, last_report_ms = 0;
   // cluster report (ksim_engine_set_report)
   bool report = false;
   DevBuf<int32_t> d_cap;   // [R][N] allocatable milli-CPU
@@ -1948,36 +1981,13 @@ struct ksim_engine {
   std::vector<DevBuf<RepAcc>> d_rep;
   std::vector<int64_t> total_gpus;
   bool rep_ready = false;      // the records of d_rep are those of a completed run (ksim_engine_get_report_parts)
-  DevBuf<RepAcc> d_rmerge;     // a node-sharded group's merged records (engine 0 of the group; k_report_merge)
-  int rmerge_n = -1;           // events they hold (-1: no group run with the report on since the events were loaded)
-  // node-sharded cluster (ksim_engine_set_shard)
-  int shard_world = 0;        // 0: not sharded
-  DevBuf<unsigned long long> d_ggran;  // a node-sharded group's exchange granules (engine 0 of the group)
-  DevBuf<ksim_hmemo::HMemoArgs> d_hgargs; // its per-shard k_hmemo arguments
-  DevBuf<unsigned long long> d_rgran;  // a node-sharded k_replay group's exchange granules (engine 0)
-  DevBuf<ReplicaDev> d_rgreps;         // its shards' replicas, and their list
-  DevBuf<int> d_rglist;
-  // one shard per process (ksim_shard_peer_handle / ksim_engine_set_shard_peers): this shard's exchange
-  // buffer (uncached device memory, exported by IPC), the peers' buffers mapped here, the run epoch
-  DevBuf<unsigned long long> d_pgran;
-  std::vector<uint8_t> pgran_handle;      // the handle ksim_shard_peer_handle returned (exports differ per call)
-  std::vector<unsigned long long*> peers;
-  std::vector<char> peer_opened;
-  int peer_epoch = 0;
-  int shard_rank = 0, node_off = 0, n_global = 0;
-  ncclComm_t comm = nullptr;  // null: in-process shard group (ksim_shard_group_run) or world 1
-  DevBuf<unsigned long long> d_send;  // this shard's record {best, nfeas, err, lo|hi}
-  DevBuf<unsigned long long> d_recv;  // [world][4] gathered records
-  DevBuf<unsigned long long*> d_ptrs; // group mode: send / recv pointer tables
-  ksim_shard_exchange_fn xfn = nullptr;  // host exchange (ksim_engine_set_shard_exchange)
-  void* xuser = nullptr;
-  std::vector<uint64_t> h_send, h_recv;  // its staging records
+  ShardState shard;            // node-sharded cluster (ksim_engine_set_shard)
   // the Random draw structure on Go's math/rand stream (ksim_engine_set_go_stream): per replica the
   // source state {vec[607], tap, feed}, empty = the hash contract
   std::vector<std::vector<unsigned long long>> go_state;
   DevBuf<unsigned long long> d_go;
-  int64_t last_steps = 0;
-  bool ran = false;      // a ksim_engine_run completed since the last set_nodes / set_typical / load_events
+  RunStats stats;        // the last run's diagnostics (ksim_run_host.hpp)
+  bool ran = false;     // a ksim_engine_run completed since the last set_nodes / set_typical / load_events
   DeschedState ds;       // the descheduling plan made from that run
   ~ksim_engine();
 };
@@ -1992,7 +2002,6 @@ static int check_gfx950(int dev) {
 }
 
 static int alloc_report(ksim_engine* e, int r);
-static void destroy_comm(ncclComm_t c);
 
 static int upload_reps(ksim_engine* e) {
   KSIM_HIP(hipMemcpyAsync(e->d_reps.p, e->reps.data(), sizeof(ReplicaDev) * e->R, hipMemcpyHostToDevice, e->stream));
@@ -2123,7 +2132,7 @@ static PlanInput plan_input(const ksim_engine* e, const RunEnv& env, const std::
     in.reps.push_back({&e->h_cls[r], &e->h_ev_cls[r], &e->h_rec[r], &e->h_tp[r], e->reps[r].typed, e->reps[r].ncpu,
                        e->reps[r].nt});
   in.N = e->N;
-  in.node_off = e->node_off;
+  in.node_off = e->shard.node_off;
   in.cus = e->cus;
   in.wgs_req = e->wgs_req;
   in.run_mode = e->run_mode;
@@ -2174,7 +2183,7 @@ static int prepare_hmemo(ksim_engine* e, const RunEnv& env, const std::vector<in
 static int upload_memo(ksim_engine* e, const PlanInput& in, const std::vector<int>& reps, int max_ev);
 
 static int prepare_memo(ksim_engine* e, const RunEnv& env, int max_ev) {
-  if (e->run_mode == 1 || e->run_mode == 2 || e->shard_world > 0) return KSIM_OK;
+  if (e->run_mode == 1 || e->run_mode == 2 || e->shard.on()) return KSIM_OK;
   std::vector<int> reps, wide, narrow;
   for (int r = 0; r < e->R; ++r)
     if (e->reps[r].policy == POL_FGD) {
@@ -2768,9 +2777,6 @@ ksim_engine::~ksim_engine() {
     if (s) (void)hipStreamSynchronize(s);
   if (stream) (void)hipStreamSynchronize(stream);
   graph.reset();
-  if (comm) destroy_comm(comm);
-  for (size_t q = 0; q < peers.size(); ++q)
-    if (peer_opened[q]) (void)hipIpcCloseMemHandle(peers[q]);
 }
 
 void ksim_engine_destroy(ksim_engine* e) { if (e) delete e; }
@@ -2789,8 +2795,8 @@ int ksim_engine_set_nodes(ksim_engine* e, int replica, const ksim_node* nodes) {
     if (s.gpu_count < 0 || s.gpu_count > kMaxGpu || s.gpu_type < 0 || s.gpu_type >= KSIM_MAX_TYPES)
       return KSIM_ERANGE;
     // sharded cluster: ranks are global and shard-contiguous (local node i has rank node_off + i)
-    if (e->shard_world > 0 && s.name_rank != (uint32_t)(e->node_off + i)) return KSIM_EINVAL;
-    const uint32_t lr = s.name_rank - (uint32_t)e->node_off;
+    if (e->shard.on() && s.name_rank != (uint32_t)(e->shard.node_off + i)) return KSIM_EINVAL;
+    const uint32_t lr = s.name_rank - (uint32_t)e->shard.node_off;
     if (lr >= (uint32_t)e->N || seen[lr]) return KSIM_EINVAL;
     if (s.cpu_alloc_milli < 0 || s.cpu_alloc_milli > 0x3fffffff) return KSIM_ERANGE;
     cap[i] = (int32_t)s.cpu_alloc_milli;
@@ -3168,7 +3174,7 @@ static int reset_state(ksim_engine* e) {
 static int alloc_report(ksim_engine* e, int r) {
   const bool on = e->report && e->d_ev[r].p;
   e->rep_ready = false;  // (new events or the report switched: the records are no run's)
-  e->rmerge_n = -1;
+  e->shard.group.rmerge_n = -1;
   const size_t ne = (size_t)std::max(e->n_events[r], 1);
   int rc = on ? e->d_snap[r].alloc(ne) : KSIM_OK;
   if (on && !rc) rc = e->d_prev[r].alloc(ne);
@@ -3187,7 +3193,7 @@ static int run_report(ksim_engine* e, int max_ev, hipStream_t st, const int* lis
   const dim3 grid((unsigned)((max_ev + ksim_rep::kDeltaBlock - 1) / ksim_rep::kDeltaBlock), (unsigned)R);
   hipLaunchKernelGGL(ksim_rep::k_report_delta, grid, dim3(ksim_rep::kDeltaBlock), 0, st,
                      (const ReplicaDev*)e->d_reps.p, (const TypDev*)e->d_tp.p, list,
-                     (e->shard_world > 1 && e->shard_rank != 0) ? 0 : 1);  // a cluster's arrivals: shard rank 0 counts them
+                     (e->shard.world > 1 && e->shard.rank != 0) ? 0 : 1);  // a cluster's arrivals: shard rank 0 counts them
   KSIM_HIP(hipGetLastError());
   // the scan over B workgroups per replica when a few replicas would leave most CUs idle behind one workgroup's pass
   // (about a CU-full of workgroups, parts of >= 2048 events; KSIM_VARIANT report_parts=0: one workgroup each)
@@ -3248,8 +3254,9 @@ static RcclApi* rccl() {
   return state == 1 ? &api : nullptr;
 }
 
-static void destroy_comm(ncclComm_t c) {
+static hipError_t destroy_comm(ncclComm_t c) {  // ShardComm's destroyer
   if (rccl()) (void)rccl()->comm_destroy(c);
+  return hipSuccess;
 }
 
 // One pod step of a sharded cluster, enqueued on `st`: local Filter+Score (k_step mode 2), the
@@ -3259,7 +3266,7 @@ static int shard_local(ksim_engine* e, hipStream_t st, const int* base, int step
   a.base = base;
   a.step_off = step_off;
   a.mode = 2;
-  a.send = e->d_send.p;
+  a.send = e->shard.d_send.p;
   hipLaunchKernelGGL(k_step, dim3(e->bpr), dim3(kBlock), 0, st, a, (const TypDev*)e->d_tp.p);
   KSIM_HIP(hipGetLastError());
   return KSIM_OK;
@@ -3268,22 +3275,22 @@ static int shard_commit(ksim_engine* e, hipStream_t st, const int* base, int ste
   StepArgs a = base_args(e);
   a.base = base;
   a.step_off = step_off;
-  a.recv = e->d_recv.p;
-  a.world = e->shard_world;
+  a.recv = e->shard.d_recv.p;
+  a.world = e->shard.world;
   hipLaunchKernelGGL(k_shard_commit, dim3(1), dim3(64), 0, st, a);
   KSIM_HIP(hipGetLastError());
   return KSIM_OK;
 }
 static int shard_exchange(ksim_engine* e, hipStream_t st) {
-  if (e->comm) {
-    const ncclResult_t r = rccl()->all_gather(e->d_send.p, e->d_recv.p, 4, ncclUint64, e->comm, st);
+  if (e->shard.exchanges_by_rccl()) {
+    const ncclResult_t r = rccl()->all_gather(e->shard.d_send.p, e->shard.d_recv.p, 4, ncclUint64, e->shard.comm, st);
     if (r != ncclSuccess) {
       std::fprintf(stderr, "ksim: ncclAllGather failed: %s\n", rccl()->error_string(r));
       return KSIM_EHIP;
     }
     return KSIM_OK;
   }
-  KSIM_HIP(hipMemcpyAsync(e->d_recv.p, e->d_send.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+  KSIM_HIP(hipMemcpyAsync(e->shard.d_recv.p, e->shard.d_send.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
   return KSIM_OK;
 }
 
@@ -3291,22 +3298,22 @@ static int shard_exchange(ksim_engine* e, hipStream_t st) {
 // stream capture accepts the collective, else enqueued eagerly.
 static int run_sharded(ksim_engine* e, int max_ev) {
   int rc;
-  if (e->xfn) {  // host exchange: the record goes through the caller's transport, one step at a time
+  ShardState& sh = e->shard;
+  if (sh.exchanges_on_host()) {  // the record goes through the caller's transport, one step at a time
     const size_t rec = 4 * sizeof(unsigned long long);
     for (int s = 0; s < max_ev; ++s) {
       if ((rc = shard_local(e, e->stream, nullptr, s))) return rc;
-      KSIM_HIP(hipMemcpyAsync(e->h_send.data(), e->d_send.p, rec, hipMemcpyDeviceToHost, e->stream));
+      KSIM_HIP(hipMemcpyAsync(sh.h_send.data(), sh.d_send.p, rec, hipMemcpyDeviceToHost, e->stream));
       KSIM_HIP(hipStreamSynchronize(e->stream));
-      if (e->xfn(e->h_send.data(), e->h_recv.data(), e->xuser) != 0) return KSIM_ESTATE;
+      if (sh.xfn(sh.h_send.data(), sh.h_recv.data(), sh.xuser) != 0) return KSIM_ESTATE;
       // the caller's gather must hold this shard's own record at its rank
-      if (std::memcmp(e->h_recv.data() + 4 * (size_t)e->shard_rank, e->h_send.data(), rec) != 0) return KSIM_ESTATE;
-      KSIM_HIP(hipMemcpyAsync(e->d_recv.p, e->h_recv.data(), rec * (size_t)e->shard_world, hipMemcpyHostToDevice,
-                              e->stream));
+      if (std::memcmp(sh.h_recv.data() + 4 * (size_t)sh.rank, sh.h_send.data(), rec) != 0) return KSIM_ESTATE;
+      KSIM_HIP(hipMemcpyAsync(sh.d_recv.p, sh.h_recv.data(), rec * (size_t)sh.world, hipMemcpyHostToDevice, e->stream));
       if ((rc = shard_commit(e, e->stream, nullptr, s))) return rc;
     }
     return KSIM_OK;
   }
-  if (e->shard_world > 1 && !e->comm) return KSIM_ESTATE;  // in-process group: ksim_shard_group_run
+  if (sh.needs_group_run()) return KSIM_ESTATE;  // in-process group: ksim_shard_group_run
   hipGraph_t g = nullptr;
   GraphExec ge;
   const int K = std::min(e->K, std::max(max_ev, 1));
@@ -3411,17 +3418,6 @@ static bool dead_skip(const ksim_engine* e, const RunEnv& env, const std::vector
   return true;
 }
 
-static void note_kernel(ksim_engine* e, const char* name) {
-  for (size_t p = 0; p < e->last_kernels.size();) {  // each name once
-    size_t q = e->last_kernels.find('+', p);
-    if (q == std::string::npos) q = e->last_kernels.size();
-    if (e->last_kernels.compare(p, q - p, name) == 0) return;
-    p = q + 1;
-  }
-  if (!e->last_kernels.empty()) e->last_kernels += '+';
-  e->last_kernels += name;
-}
-
 // What the run planner (ksim_plan.hpp make_run_plan) reads of the engine, once prepare_memo has made the FGD plans.
 static RunPlanInput run_plan_input(const ksim_engine* e, const RunEnv& env) {
   RunPlanInput in;
@@ -3454,10 +3450,10 @@ static std::vector<int> group_reps(const RunPlan& plan, const PlanGroup& g) {
 
 // ---- the launchers: one per kernel family ----
 // The diagnostics of one replay launch (last_run_kernels, last_run_wgs, last_run_path): K <= 0 leaves the width,
-// replicas (nullable) is the kernel's replica counter.
+// replicas (nullable) is the kernel's replica counter in e->stats.
 static void note_launch(ksim_engine* e, const char* name, int K, int* replicas, int Rg) {
-  note_kernel(e, name);
-  if (K > 0) e->last_K = K;
+  note_kernel(e->stats, name);
+  if (K > 0) e->stats.K = K;
   if (replicas) *replicas += Rg;
 }
 
@@ -3486,7 +3482,7 @@ static int launch_random_go(ksim_engine* e, const PlanGroup& g, hipStream_t gs) 
     hipLaunchKernelGGL(ksim_random_go::k_random_go<false>, dim3(g.count), dim3(ksim_random_go::kBlock), lds, gs, ga);
   }
   KSIM_HIP(hipGetLastError());
-  note_launch(e, "k_random_go", 0, &e->last_rgo, g.count);
+  note_launch(e, "k_random_go", 0, &e->stats.rgo, g.count);
   return KSIM_OK;
 }
 
@@ -3511,7 +3507,7 @@ static int overlap_queue(ksim_engine* e, const RunEnv& env, const RunPlan& plan,
   KSIM_HIP(hipMemsetAsync(e->d_done.p, 0, 2 * sizeof(unsigned long long), gs));  // tickets; entries keep epochs
   KSIM_HIP(hipEventRecord(e->ev_ovl, gs));
   *overlapped = true;
-  e->last_ovl += g.count;
+  e->stats.ovl += g.count;
   e->done_epoch = e->done_epoch % 0x7fffffffu + 1;
   sa.done = e->d_done.p;
   sa.epoch = e->done_epoch;
@@ -3535,7 +3531,7 @@ static int launch_scan1(ksim_engine* e, const RunEnv& env, const RunPlan& plan, 
   }
   void* params[] = {(void*)&sa};
   KSIM_HIP(hipLaunchKernel(f, dim3(g.count), dim3(ksim_scan1::kBlock), params, g.lds, gs));
-  note_launch(e, mix ? "k_scan1_mix" : "k_scan1", 1, &e->last_scan1, g.count);
+  note_launch(e, mix ? "k_scan1_mix" : "k_scan1", 1, &e->stats.scan1, g.count);
   return KSIM_OK;
 }
 
@@ -3555,11 +3551,11 @@ static int launch_gated(ksim_engine* e, bool gate, int n, const char* what,
   // stderr -- it orders work, it decides nothing)
   const auto t0 = std::chrono::steady_clock::now();
   volatile int* fl = e->started.h;
-  if (e->last_gate == 0) e->last_gate = 1;
+  if (e->stats.gate == 0) e->stats.gate = 1;
   for (int w = 0; w < n;) {
     if (fl[w] == epoch) { ++w; continue; }
     if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-      e->last_gate = -1;
+      e->stats.gate = -1;
       ++e->gate_timeouts;
       std::fprintf(stderr, "ksim: residency gate given up after 2 s (%d of %d %s workgroups started); the next "
                    "groups launch unordered\n", w, n, what);
@@ -3581,7 +3577,7 @@ static int launch_memo_group(ksim_engine* e, const RunEnv& env, const RunPlan& p
     return launch_memo(e, env, pl, g.count, g.first, max_ev, gs, flags, epoch);
   });
   if (rc) return rc;
-  note_launch(e, pl.hkeys ? "k_memo_hkeys" : "k_memo", pl.K, &e->last_memo, g.count);
+  note_launch(e, pl.hkeys ? "k_memo_hkeys" : "k_memo", pl.K, &e->stats.memo, g.count);
   if (env.timers()) std::fprintf(stderr, "ksim memo%s: %d replicas, K=%d, Cw=%d, F waves %d, LDS %zu B\n",
                                  pl.decider ? " (decider)" : "", g.count, pl.K, pl.Cw, pl.nfw, pl.lds);
   return KSIM_OK;
@@ -3599,7 +3595,7 @@ static int launch_hmemo_group(ksim_engine* e, const RunEnv& env, const RunPlan& 
     return launch_hmemo(e, env, g.count, g.first, max_ev, gs, flags, epoch, gated);
   });
   if (rc) return rc;
-  note_launch(e, K == 1 ? "k_hmemo" : "k_hmemo_wide", K, &e->last_hmemo, g.count);
+  note_launch(e, K == 1 ? "k_hmemo" : "k_hmemo_wide", K, &e->stats.hmemo, g.count);
   return KSIM_OK;
 }
 
@@ -3667,7 +3663,7 @@ static int launch_replay(ksim_engine* e, const RunEnv& env, const RunPlan& plan,
   ksim_replay::ReplayArgs ra = replay_args(e->d_reps.p, e->d_replist.p + g.first, e->N, K, S, e->d_gran.p,
                                            plan.any_delete ? e->d_hist.p : nullptr, max_ev, e->d_fail.p,
                                            dead_skip(e, env, group_reps(plan, g)), 0);
-  ra.pm_c = e->last_pf_memo = replay_pf_memo(e, env, plan, g, K, S, &lds);
+  ra.pm_c = replay_pf_memo(e, env, plan, g, K, S, &lds);
   ra.pm_ver0 = env.pf_memo_ver0 > 0 && env.pf_memo_ver0 < (long)ksim_replay::kPmInvalid ? (unsigned)env.pf_memo_ver0 : 0u;
   ra.pf_guess = env.pf_guess ? 1 : 0;
   if (profile) {
@@ -3776,8 +3772,7 @@ static int run_persistent(ksim_engine* e, const RunEnv& env, int max_ev) {
   const RunPlan plan = make_run_plan(run_plan_input(e, env));
   int rc = upload_go_states(e, plan);
   if (rc) return rc;
-  e->last_memo = e->last_hmemo = e->last_rgo = e->last_scan1 = 0;
-  e->last_launches = (int)plan.groups.size();
+  e->stats.launches = (int)plan.groups.size();
   KSIM_HIP(hipMemcpyAsync(e->d_replist.p, plan.order.data(), sizeof(int) * plan.order.size(), hipMemcpyHostToDevice, e->stream));
   KSIM_HIP(hipMemsetAsync(e->d_fail.p, 0, sizeof(int), e->stream));
   if (plan.concurrent && (rc = fork_streams(e, env))) return rc;
@@ -3801,7 +3796,7 @@ static int run_persistent(ksim_engine* e, const RunEnv& env, int max_ev) {
   }
   if (plan.concurrent && e->report && (rc = launch_group_reports(e, plan, ovl_group))) return rc;
   if ((rc = record_group_times(e, env, plan, used))) return rc;
-  e->last_streams = __builtin_popcount(used);
+  e->stats.streams = __builtin_popcount(used);
   return plan.concurrent ? join_streams(e, used) : KSIM_OK;
 }
 
@@ -3829,11 +3824,7 @@ int ksim_engine_run(ksim_engine* e) {
   e->ds.invalidate();
   e->grp_rev_used = 0;
   e->tev_used = 0u;  // KSIM_GROUP_TIMES: only run_persistent's concurrent groups record side-stream ends
-  e->last_launches = 0;
-  e->last_streams = 0;
-  e->last_gate = 0;
-  e->last_ovl = 0;
-  e->last_kernels.clear();
+  e->stats = RunStats{};
   int rc = prepare_memo(e, env, max_ev);
   if (rc) return rc;
   KSIM_HIP(hipEventRecord(e->ev0, e->stream));
@@ -3845,14 +3836,14 @@ int ksim_engine_run(ksim_engine* e) {
   for (int r = 0; r < e->R; ++r)
     if (is_pwr_policy(e->reps[r].policy) && !e->pw_set[r]) return KSIM_ESTATE;
   for (int r = 0; r < e->R; ++r)  // Go-stream Random: the persistent path, best / worst / random selectors
-    if (go_random(e, r) && (step_path || e->shard_world > 0 ||
+    if (go_random(e, r) && (step_path || e->shard.on() ||
                             (e->reps[r].gpusel != SEL_BEST && e->reps[r].gpusel != SEL_WORST && e->reps[r].gpusel != SEL_RANDOM)))
       return KSIM_ENOTSUP;
-  if (e->shard_world > 0 && !e->peers.empty()) rc = run_hmemo_peer(e, env, max_ev);
-  else if (e->shard_world > 0) rc = any_pwr(e) ? KSIM_ENOTSUP : run_sharded(e, max_ev);
+  if (e->shard.runs_peer()) rc = run_hmemo_peer(e, env, max_ev);
+  else if (e->shard.on()) rc = any_pwr(e) ? KSIM_ENOTSUP : run_sharded(e, max_ev);
   else rc = step_path ? run_graph(e, max_ev) : run_persistent(e, env, max_ev);
-  if (!rc && e->shard_world > 0) note_kernel(e, !e->peers.empty() ? "k_hmemo_wide" : "k_step");
-  if (!rc && step_path) note_kernel(e, any_pwr(e) ? "k_step+k_step_pwr" : "k_step");
+  if (!rc && e->shard.on()) note_kernel(e->stats, e->shard.runs_peer() ? "k_hmemo_wide" : "k_step");
+  if (!rc && step_path) note_kernel(e->stats, any_pwr(e) ? "k_step+k_step_pwr" : "k_step");
   if (rc) return rc;
   KSIM_HIP(hipEventRecord(e->ev_mid, e->stream));
   if (e->report && !e->report_done) {
@@ -3864,12 +3855,12 @@ int ksim_engine_run(ksim_engine* e) {
   float ms = 0, rms = 0;
   KSIM_HIP(hipEventElapsedTime(&ms, e->ev0, e->ev1));
   KSIM_HIP(hipEventElapsedTime(&rms, e->ev_mid, e->ev1));
-  e->last_ms = ms;
-  e->last_report_ms = e->report ? rms : 0.0;
+  e->stats.ms = ms;
+  e->stats.report_ms = e->report ? rms : 0.0;
   for (int g = 0; g < e->grp_rev_used; ++g) {  // concurrent groups: each group's report on its side stream
     float gms = 0.f;
     KSIM_HIP(hipEventElapsedTime(&gms, e->grp_rev[2 * g], e->grp_rev[2 * g + 1]));
-    e->last_report_ms += gms;
+    e->stats.report_ms += gms;
   }
   if (e->tev_used) {  // KSIM_GROUP_TIMES=1
     std::fprintf(stderr, "ksim group times (ms from the fork to each side stream's end):");
@@ -3886,9 +3877,9 @@ int ksim_engine_run(ksim_engine* e) {
     }
     std::fprintf(stderr, " run %.3f\n", ms);
   }
-  e->last_steps = max_ev;
-  e->last_step_path = step_path;
-  if (!step_path && e->shard_world == 0) {
+  e->stats.steps = max_ev;
+  e->stats.step_path = step_path;
+  if (!step_path && e->shard.world == 0) {
     int fail = 0;
     KSIM_HIP(hipMemcpy(&fail, e->d_fail.p, sizeof(int), hipMemcpyDeviceToHost));
     if (fail & 2) return KSIM_ERANGE;  // a raw PWR score outside the 24-bit key field
@@ -3915,28 +3906,29 @@ int ksim_engine_set_shard(ksim_engine* e, int rank, int world, int node_offset, 
   if (!e || world < 1 || world > 16 || rank < 0 || rank >= world || node_offset < 0 || n_global < e->N ||
       node_offset + e->N > n_global || n_global > kMaxRank || e->R != 1)
     return KSIM_EINVAL;
-  if (e->shard_world > 0) return KSIM_ESTATE;  // once per engine, before set_nodes
+  if (e->shard.on()) return KSIM_ESTATE;  // once per engine, before set_nodes
   KSIM_HIP(hipSetDevice(e->device));
   if (comm_id) {
     RcclApi* r = rccl();
     if (!r) return KSIM_ENOTSUP;
     ncclUniqueId id;
     std::memcpy(id.internal, comm_id, KSIM_SHARD_ID_BYTES);
-    const ncclResult_t nr = r->comm_init_rank(&e->comm, world, id, rank);
+    const ncclResult_t nr = r->comm_init_rank(&e->shard.comm.h, world, id, rank);
     if (nr != ncclSuccess) {
       std::fprintf(stderr, "ksim: ncclCommInitRank failed: %s\n", r->error_string(nr));
-      e->comm = nullptr;
+      e->shard.comm.h = nullptr;
       return KSIM_EHIP;
     }
   }
-  int rc = e->d_send.alloc(4);
-  if (!rc) rc = e->d_recv.alloc(4 * (size_t)world);
-  if (!rc) rc = e->d_send.zero(e->stream);
+  int rc = e->shard.d_send.alloc(4);
+  if (!rc) rc = e->shard.d_recv.alloc(4 * (size_t)world);
+  if (!rc) rc = e->shard.d_send.zero(e->stream);
   if (rc) return rc;
-  e->shard_world = world;
-  e->shard_rank = rank;
-  e->node_off = node_offset;
-  e->n_global = n_global;
+  e->shard.transport = comm_id ? ShardTransport::rccl : ShardTransport::group;
+  e->shard.world = world;
+  e->shard.rank = rank;
+  e->shard.node_off = node_offset;
+  e->shard.n_global = n_global;
   e->reps[0].node_off = node_offset;
   rc = upload_reps(e);
   if (rc) return rc;
@@ -3946,11 +3938,14 @@ int ksim_engine_set_shard(ksim_engine* e, int rank, int world, int node_offset, 
 
 int ksim_engine_set_shard_exchange(ksim_engine* e, ksim_shard_exchange_fn fn, void* user) {
   if (!e) return KSIM_EINVAL;
-  if (e->shard_world < 1 || e->comm) return KSIM_ESTATE;  // after set_shard, and not beside RCCL
-  e->xfn = fn;
-  e->xuser = user;
-  e->h_send.assign(4, 0);
-  e->h_recv.assign(4 * (size_t)e->shard_world, 0);
+  ShardState& sh = e->shard;
+  if (!sh.takes_exchange_fn()) return KSIM_ESTATE;  // after set_shard, and not beside RCCL
+  sh.xfn = fn;
+  sh.xuser = user;
+  sh.h_send.assign(4, 0);
+  sh.h_recv.assign(4 * (size_t)sh.world, 0);
+  // a null function takes the host exchange away again; mapped peers stay the transport whatever is installed
+  if (!sh.runs_peer()) sh.transport = fn ? ShardTransport::host : ShardTransport::group;
   return KSIM_OK;
 }
 
@@ -3976,49 +3971,45 @@ static int peer_device(const uint8_t* hd) {
 
 int ksim_shard_peer_handle(ksim_engine* e, uint8_t* out) {
   if (!e || !out) return KSIM_EINVAL;
-  if (e->shard_world < 1 || e->comm || e->xfn) return KSIM_ESTATE;
+  ShardState& sh = e->shard;
+  if (!sh.in_process()) return KSIM_ESTATE;
   KSIM_HIP(hipSetDevice(e->device));
-  if (!e->d_pgran.p) {
+  if (!sh.d_pgran.p) {
     // uncached device memory: the peers' stores land in it over xGMI and the local polls read it there
-    int rc = e->d_pgran.alloc(kPeerGranBytes / sizeof(unsigned long long), hipDeviceMallocUncached);
-    if (!rc) rc = e->d_pgran.zero(e->stream);
+    int rc = sh.d_pgran.alloc(kPeerGranBytes / sizeof(unsigned long long), hipDeviceMallocUncached);
+    if (!rc) rc = sh.d_pgran.zero(e->stream);
     if (rc) return rc;
     KSIM_HIP(hipStreamSynchronize(e->stream));
   }
-  if (e->pgran_handle.empty()) {
+  if (sh.pgran_handle.empty()) {
     hipIpcMemHandle_t h;
-    KSIM_HIP(hipIpcGetMemHandle(&h, e->d_pgran.p));
+    KSIM_HIP(hipIpcGetMemHandle(&h, sh.d_pgran.p));
     static_assert(sizeof(hipIpcMemHandle_t) + 20 <= KSIM_SHARD_HANDLE_BYTES, "IPC handle size");
     hipDeviceProp_t prop;
     KSIM_HIP(hipGetDeviceProperties(&prop, e->device));
     const uint32_t tail[5] = {kPeerMagic, (uint32_t)prop.pciDomainID, (uint32_t)prop.pciBusID,
                               (uint32_t)prop.pciDeviceID, (uint32_t)getpid()};
-    e->pgran_handle.assign(KSIM_SHARD_HANDLE_BYTES, 0);
-    std::memcpy(e->pgran_handle.data(), &h, sizeof h);
-    std::memcpy(e->pgran_handle.data() + sizeof h, tail, sizeof tail);
+    sh.pgran_handle.assign(KSIM_SHARD_HANDLE_BYTES, 0);
+    std::memcpy(sh.pgran_handle.data(), &h, sizeof h);
+    std::memcpy(sh.pgran_handle.data() + sizeof h, tail, sizeof tail);
   }
-  std::memcpy(out, e->pgran_handle.data(), KSIM_SHARD_HANDLE_BYTES);
+  std::memcpy(out, sh.pgran_handle.data(), KSIM_SHARD_HANDLE_BYTES);
   return KSIM_OK;
 }
 
 int ksim_engine_set_shard_peers(ksim_engine* e, const uint8_t* handles) {
   if (!e || !handles) return KSIM_EINVAL;
-  if (e->shard_world < 1 || !e->d_pgran.p || e->pgran_handle.empty() || !e->peers.empty()) return KSIM_ESTATE;
+  ShardState& sh = e->shard;
+  if (!sh.can_map_peers()) return KSIM_ESTATE;  // after ksim_shard_peer_handle, once
   KSIM_HIP(hipSetDevice(e->device));
-  const int world = e->shard_world;
+  const int world = sh.world;
   if (const long ep = test_knob("peer_epoch0", 0))  // tests: start the run epoch near its wrap
-    e->peer_epoch = (int)(ep & 0xffffff);
-  e->peers.assign(world, nullptr);
-  e->peer_opened.assign(world, 0);
-  if (e->pgran_handle.empty() ||
-      std::memcmp(handles + (size_t)e->shard_rank * KSIM_SHARD_HANDLE_BYTES, e->pgran_handle.data(),
-                  KSIM_SHARD_HANDLE_BYTES) != 0) {
-    e->peers.clear();
+    sh.peer_epoch = (int)(ep & 0xffffff);
+  if (std::memcmp(handles + (size_t)sh.rank * KSIM_SHARD_HANDLE_BYTES, sh.pgran_handle.data(), KSIM_SHARD_HANDLE_BYTES) != 0)
     return KSIM_EINVAL;  // this shard's own handle must sit at its rank
-  }
   // every peer's device first: visible here and reachable (xGMI / P2P), or nothing is mapped
   for (int q = 0; q < world; ++q) {
-    if (q == e->shard_rank) continue;
+    if (q == sh.rank) continue;
     const int pd = peer_device(handles + (size_t)q * KSIM_SHARD_HANDLE_BYTES);
     int can = pd == e->device ? 1 : 0;
     if (pd >= 0 && pd != e->device) {
@@ -4031,32 +4022,17 @@ int ksim_engine_set_shard_peers(ksim_engine* e, const uint8_t* handles) {
       std::fprintf(stderr, "ksim: shard %d's exchange buffer is %s\n", q,
                    pd == -2 ? "a malformed handle" : pd == -1 ? "on a GPU not visible in this process"
                                                                : "on a GPU without a peer path from this one");
-      e->peers.clear();
-      e->peer_opened.clear();
       return pd == -2 ? KSIM_EINVAL : KSIM_EPEER;
     }
   }
-  for (int q = 0; q < world; ++q) {
-    if (q == e->shard_rank) {
-      e->peers[q] = e->d_pgran.p;
-      continue;
-    }
-    hipIpcMemHandle_t h;
-    std::memcpy(&h, handles + (size_t)q * KSIM_SHARD_HANDLE_BYTES, sizeof h);
-    void* p = nullptr;
-    const hipError_t r = hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess);
-    if (r != hipSuccess) {
-      std::fprintf(stderr, "ksim: hipIpcOpenMemHandle (shard %d): %s\n", q, hipGetErrorString(r));
-      (void)hipGetLastError();
-      for (int k = 0; k < q; ++k)
-        if (e->peer_opened[k]) (void)hipIpcCloseMemHandle(e->peers[k]);
-      e->peers.clear();
-      e->peer_opened.clear();
-      return KSIM_EHIP;
-    }
-    e->peers[q] = reinterpret_cast<unsigned long long*>(p);
-    e->peer_opened[q] = 1;
+  int bad = -1;
+  hipError_t why = hipSuccess;
+  if (const int rc = sh.peers.open(handles, KSIM_SHARD_HANDLE_BYTES, world, sh.rank, sh.d_pgran.p, &bad, &why)) {
+    std::fprintf(stderr, "ksim: hipIpcOpenMemHandle (shard %d): %s\n", bad, hipGetErrorString(why));
+    (void)hipGetLastError();
+    return rc;
   }
+  sh.transport = ShardTransport::peer;
   return KSIM_OK;
 }
 
@@ -4073,9 +4049,23 @@ static int reset_shard_state(ksim_engine* e, hipStream_t st, bool results) {
   return KSIM_OK;
 }
 
-// The end of an in-process group's run on engine 0's stream: the closing event, the wait, the fail word of the
-// group's one launch, then the run's time and diagnostics on every engine.  K = 0: the per-pod k_step path, which
-// has no fail word and no width.
+// The end of a node-sharded replay on e's stream: the closing event, the wait, the fail word of its one launch
+// (fail_word false: the per-pod k_step path has none) -- KSIM_ESTATE for a replay that gave up -- and the time from
+// ev0 to the closing event into e->stats.
+static int end_replay(ksim_engine* e, hipEvent_t closing, bool fail_word) {
+  KSIM_HIP(hipEventRecord(closing, e->stream));
+  KSIM_HIP(hipStreamSynchronize(e->stream));
+  int fail = 0;
+  if (fail_word) KSIM_HIP(hipMemcpy(&fail, e->d_fail.p, sizeof(int), hipMemcpyDeviceToHost));
+  if (fail) return KSIM_ESTATE;
+  float ms = 0;
+  KSIM_HIP(hipEventElapsedTime(&ms, e->ev0, closing));
+  e->stats.ms = ms;
+  return KSIM_OK;
+}
+
+// The end of an in-process group's run on engine 0's stream: end_replay, then the run's time and diagnostics on every
+// engine.  K = 0: the per-pod k_step path, which has no fail word and no width.
 //
 // With the cluster report on (every shard or none: ksim_shard_group_run checks), the report follows the replay once
 // its fail word is read clean (a replay that gave up leaves events without a snapshot): every shard's own report
@@ -4086,20 +4076,16 @@ static int finish_group_run(ksim_engine* const* engines, int world, int max_ev, 
   ksim_engine* e0 = engines[0];
   hipStream_t st = e0->stream;
   const bool report = e0->report;
-  KSIM_HIP(hipEventRecord(report ? e0->ev_mid : e0->ev1, st));
-  KSIM_HIP(hipStreamSynchronize(st));
-  int fail = 0;
-  if (K > 0) KSIM_HIP(hipMemcpy(&fail, e0->d_fail.p, sizeof(int), hipMemcpyDeviceToHost));
-  if (fail) return KSIM_ESTATE;
-  float rms = 0;
+  int rc = end_replay(e0, report ? e0->ev_mid : e0->ev1, K > 0);
+  if (rc) return rc;
+  RunStats& s = e0->stats;
   if (report) {
-    int rc;
     ksim_rep::MergeArgs ma{};
     for (int k = 0; k < world; ++k) {
       if ((rc = run_report(engines[k], max_ev, st, nullptr, 1))) return rc;
       ma.part[k] = engines[k]->d_rep[0].p;
     }
-    if ((rc = e0->d_rmerge.ensure((size_t)std::max(max_ev, 1)))) return rc;
+    if ((rc = e0->shard.group.d_rmerge.ensure((size_t)std::max(max_ev, 1)))) return rc;
     const bool times = read_env().group_times;  // KSIM_GROUP_TIMES=1: the merge's share of the report, on stderr
     if (times) {
       if ((rc = e0->tev_fork.ensure())) return rc;
@@ -4108,27 +4094,56 @@ static int finish_group_run(ksim_engine* const* engines, int world, int max_ev, 
     if (max_ev > 0) {
       const long long lanes = (long long)max_ev * ksim_rep::kMergeLanes;
       hipLaunchKernelGGL(ksim_rep::k_report_merge, dim3((unsigned)((lanes + ksim_rep::kMergeBlock - 1) / ksim_rep::kMergeBlock)),
-                         dim3(ksim_rep::kMergeBlock), 0, st, ma, world, max_ev, e0->d_rmerge.p);
+                         dim3(ksim_rep::kMergeBlock), 0, st, ma, world, max_ev, e0->shard.group.d_rmerge.p);
       KSIM_HIP(hipGetLastError());
     }
     KSIM_HIP(hipEventRecord(e0->ev1, st));
     KSIM_HIP(hipStreamSynchronize(st));
+    float rms = 0, ms = 0;
     KSIM_HIP(hipEventElapsedTime(&rms, e0->ev_mid, e0->ev1));
-    e0->rmerge_n = max_ev;
+    KSIM_HIP(hipEventElapsedTime(&ms, e0->ev0, e0->ev1));  // the run's time takes the report in
+    s.report_ms = rms;
+    s.ms = ms;
+    e0->shard.group.rmerge_n = max_ev;
     float mms = 0;
     if (times && hipEventElapsedTime(&mms, e0->tev_fork, e0->ev1) == hipSuccess)
       std::fprintf(stderr, "ksim group report times (ms): %d shards' reports %.3f; merge %.3f\n", world, rms - mms, mms);
   }
-  float ms = 0;
-  KSIM_HIP(hipEventElapsedTime(&ms, e0->ev0, e0->ev1));
-  for (int k = 0; k < world; ++k) {
-    engines[k]->last_report_ms = rms;
+  s.steps = max_ev;
+  s.K = K;
+  s.hmemo = hmemo ? 1 : 0;
+  s.kernels = kernel;
+  for (int k = 0; k < world; ++k) {  // one run: the same diagnostics on every engine of the group
+    if (k > 0) engines[k]->stats = s;
     engines[k]->rep_ready = report;
-    engines[k]->last_ms = ms;
-    engines[k]->last_steps = max_ev;
-    if (K > 0) engines[k]->last_K = K;
-    if (hmemo) engines[k]->last_hmemo = 1;
-    engines[k]->last_kernels = kernel;
+  }
+  return KSIM_OK;
+}
+
+// One shard's k_hmemo launch arguments, for its K slices of S ranks among the Kt columns of the exchange through
+// `gran`, the shard's first column being wbase: the replica list and the plan on the shard's own stream (the plan is
+// not the unsharded one: the cache is dropped), then on `st` the shard back to its initial state and the keys, and the
+// bind history when the stream deletes.  KSIM_OK with *planned = false: no plan for these slices, nothing enqueued on st.
+static int shard_hmemo_args(ksim_engine* e, const RunEnv& env, int max_ev, int K, int S, int Kt, int wbase,
+                            unsigned long long* gran, hipStream_t st, ksim_hmemo::HMemoArgs* a, bool* planned) {
+  const int stride = std::max(max_ev, 1);
+  const int zero = 0;
+  KSIM_HIP(hipMemcpyAsync(e->d_replist.p, &zero, sizeof(int), hipMemcpyHostToDevice, e->stream));
+  int rc = prepare_hmemo(e, env, std::vector<int>{0}, max_ev, K, S);
+  if (rc) return rc;
+  if (!(*planned = e->hmemo.ok)) return KSIM_OK;
+  e->mplan_dirty = true;
+  if (st != e->stream) KSIM_HIP(hipStreamSynchronize(e->stream));  // the group's stream is engine 0's
+  if ((rc = reset_shard_state(e, st, true))) return rc;
+  if ((rc = hmemo_init_keys(e, 1, 0, st, e->shard.node_off))) return rc;
+  *a = hmemo_args(e, env, 0, stride);
+  a->roff = e->shard.node_off;
+  a->wbase = wbase;
+  a->Ktot = Kt;
+  a->gran = gran;
+  if (e->has_delete[0]) {
+    if ((rc = e->hmemo.hist.ensure((size_t)K * stride))) return rc;
+    a->hist = e->hmemo.hist.p;
   }
   return KSIM_OK;
 }
@@ -4138,34 +4153,22 @@ static int finish_group_run(ksim_engine* const* engines, int world, int max_ev, 
 static int run_hmemo_peer(ksim_engine* e, const RunEnv& env, int max_ev) {
   using namespace ksim_hmemo;
   if (e->R != 1 || e->reps[0].policy != POL_FGD || go_random(e, 0) || !score_table()) return KSIM_ENOTSUP;
-  const int world = e->shard_world;
-  const ShardSlices sl = hmemo_peer_slices(e->n_global, world, e->N);
+  ShardState& sh = e->shard;
+  const int world = sh.world;
+  const ShardSlices sl = hmemo_peer_slices(sh.n_global, world, e->N);
   if (!sl.ok) return KSIM_ENOTSUP;
-  const int K = sl.K, S = sl.S, Kt = world * K;
-  const int stride = std::max(max_ev, 1);
+  const int K = sl.K, Kt = world * K;
   hipStream_t st = e->stream;
-  const int zero = 0;
-  KSIM_HIP(hipMemcpyAsync(e->d_replist.p, &zero, sizeof(int), hipMemcpyHostToDevice, st));
-  int rc = prepare_hmemo(e, env, std::vector<int>{0}, max_ev, K, S);
+  HMemoArgs a;
+  bool planned = false;
+  int rc = shard_hmemo_args(e, env, max_ev, K, sl.S, Kt, sh.rank * K, sh.d_pgran.p, st, &a, &planned);
   if (rc) return rc;
-  if (!e->hmemo.ok) return KSIM_ENOTSUP;
-  e->mplan_dirty = true;
-  if ((rc = reset_shard_state(e, st, true))) return rc;
-  if ((rc = hmemo_init_keys(e, 1, 0, st, e->node_off))) return rc;
-  HMemoArgs a = hmemo_args(e, env, 0, stride);
-  a.roff = e->node_off;
-  a.wbase = e->shard_rank * K;
-  a.Ktot = Kt;
-  a.gran = e->d_pgran.p;
+  if (!planned) return KSIM_ENOTSUP;
   a.npeer = world;
-  e->peer_epoch = (e->peer_epoch + 1) & 0xffffff;  // every rank runs the same runs: the same epoch (24 bits)
-  if (e->peer_epoch == 0) e->peer_epoch = 1;
-  a.epoch = e->peer_epoch;
-  for (int q = 0; q < world; ++q) a.peer[q] = e->peers[q];
-  if (e->has_delete[0]) {
-    if ((rc = e->hmemo.hist.ensure((size_t)K * stride))) return rc;
-    a.hist = e->hmemo.hist.p;
-  }
+  sh.peer_epoch = (sh.peer_epoch + 1) & 0xffffff;  // every rank runs the same runs: the same epoch (24 bits)
+  if (sh.peer_epoch == 0) sh.peer_epoch = 1;
+  a.epoch = sh.peer_epoch;
+  for (int q = 0; q < world; ++q) a.peer[q] = sh.peers.ptr[q];
   KSIM_HIP(hipMemsetAsync(e->d_fail.p, 0, sizeof(int), st));
   const void* f = hmemo_kernel(hmemo_form(kHPeer, Kt, false, a.delay, false));
   if (K > resident_cap(e, f, e->hmemo.plan.lds)) return KSIM_ERANGE;
@@ -4175,17 +4178,9 @@ static int run_hmemo_peer(ksim_engine* e, const RunEnv& env, int max_ev) {
   // takes the device's one global-wave-sync resource, which a second shard process on the same device
   // would wait for behind the first's persistent kernel
   if ((rc = launch_persistent(f, K, kHBlock, e->hmemo.plan.lds, st, false, a, tpp))) return rc;
-  KSIM_HIP(hipEventRecord(e->ev1, st));
-  KSIM_HIP(hipStreamSynchronize(st));
-  int fail = 0;
-  KSIM_HIP(hipMemcpy(&fail, e->d_fail.p, sizeof(int), hipMemcpyDeviceToHost));
-  if (fail) return KSIM_ESTATE;
-  float ms = 0;
-  KSIM_HIP(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-  e->last_ms = ms;
-  e->last_steps = max_ev;
-  e->last_K = K;
-  e->last_hmemo = 1;
+  if ((rc = end_replay(e, e->ev1, true))) return rc;  // (ksim_engine_run's tail times the run to the end of its report)
+  e->stats.K = K;
+  e->stats.hmemo = 1;
   return KSIM_OK;
 }
 
@@ -4238,12 +4233,12 @@ static int run_replay_group(ksim_engine* const* engines, int world, const RunEnv
   hipStream_t st = e0->stream;
   KSIM_HIP(hipSetDevice(e0->device));
   int rc;
-  if ((rc = e0->d_rgran.ensure((size_t)2 * 256 * kGranW))) return rc;
-  if ((rc = e0->d_rgreps.ensure(16))) return rc;
-  if (!e0->d_rglist.p) {
+  if ((rc = e0->shard.group.d_rgran.ensure((size_t)2 * 256 * kGranW))) return rc;
+  if ((rc = e0->shard.group.d_rgreps.ensure(16))) return rc;
+  if (!e0->shard.group.d_rglist.p) {
     std::vector<int> id(16);
     std::iota(id.begin(), id.end(), 0);
-    if ((rc = e0->d_rglist.upload(id, st))) return rc;
+    if ((rc = e0->shard.group.d_rglist.upload(id, st))) return rc;
     KSIM_HIP(hipStreamSynchronize(st));  // `id` is pageable
   }
   bool skip = true;
@@ -4251,12 +4246,12 @@ static int run_replay_group(ksim_engine* const* engines, int world, const RunEnv
     ksim_engine* e = engines[k];
     KSIM_HIP(hipStreamSynchronize(e->stream));
     if ((rc = reset_shard_state(e, st, true))) return rc;
-    KSIM_HIP(hipMemcpyAsync(e0->d_rgreps.p + k, e->d_reps.p, sizeof(ReplicaDev), hipMemcpyDeviceToDevice, st));
+    KSIM_HIP(hipMemcpyAsync(e0->shard.group.d_rgreps.p + k, e->d_reps.p, sizeof(ReplicaDev), hipMemcpyDeviceToDevice, st));
     skip = skip && dead_skip(e, env, std::vector<int>{0});
   }
   ReplayArgs ra =
-      replay_args(e0->d_rgreps.p, e0->d_rglist.p, N, K, S, e0->d_rgran.p, nullptr, max_ev, e0->d_fail.p, skip, Kt);
-  KSIM_HIP(hipMemsetAsync(e0->d_rgran.p, 0, sizeof(unsigned long long) * 2 * (size_t)Kt * kGranW, st));
+      replay_args(e0->shard.group.d_rgreps.p, e0->shard.group.d_rglist.p, N, K, S, e0->shard.group.d_rgran.p, nullptr, max_ev, e0->d_fail.p, skip, Kt);
+  KSIM_HIP(hipMemsetAsync(e0->shard.group.d_rgran.p, 0, sizeof(unsigned long long) * 2 * (size_t)Kt * kGranW, st));
   KSIM_HIP(hipMemsetAsync(e0->d_fail.p, 0, sizeof(int), st));
   KSIM_HIP(hipEventRecord(e0->ev0, st));
   const TypDev* tp = e0->d_tp.p;  // (the cheap policies read no typical table)
@@ -4271,57 +4266,35 @@ static int run_hmemo_group(ksim_engine* const* engines, int world, const RunEnv&
   using namespace ksim_hmemo;
   *done = false;
   ksim_engine* e0 = engines[0];
-  const int stride = std::max(max_ev, 1);
+  ShardState::Group& grp = e0->shard.group;
   int nmax = 1;
   for (int k = 0; k < world; ++k) nmax = std::max(nmax, engines[k]->N);
   const ShardSlices sl = hmemo_group_slices(nmax, world, e0->cus);
   if (!sl.ok) return KSIM_OK;
-  const int K = sl.K, S = sl.S, Kt = world * K;
-  std::vector<HMemoArgs> args(world);
-  size_t lds = 0;
-  for (int k = 0; k < world; ++k) {
-    ksim_engine* e = engines[k];
-    const int zero = 0;
-    KSIM_HIP(hipMemcpyAsync(e->d_replist.p, &zero, sizeof(int), hipMemcpyHostToDevice, e->stream));
-    int rc = prepare_hmemo(e, env, std::vector<int>{0}, max_ev, K, S);
-    if (rc) return rc;
-    if (!e->hmemo.ok) return KSIM_OK;
-    e->mplan_dirty = true;  // the unsharded plan is not this one
-    lds = std::max(lds, e->hmemo.plan.lds);
-  }
-  const void* f = hmemo_kernel(hmemo_form(kHGroup, Kt, false, env.hdelay, false));
-  if (Kt > resident_cap(e0, f, lds)) return KSIM_OK;
+  const int K = sl.K, Kt = world * K;
   hipStream_t st = e0->stream;
   KSIM_HIP(hipSetDevice(e0->device));
   int rc;
-  if ((rc = e0->d_ggran.ensure((size_t)2 * 256 * 2))) return rc;
-  if ((rc = e0->d_hgargs.ensure(16))) return rc;
+  if ((rc = grp.d_ggran.ensure((size_t)2 * 256 * 2))) return rc;
+  if ((rc = grp.d_hgargs.ensure(16))) return rc;
+  std::vector<HMemoArgs> args(world);
+  size_t lds = 0;
   for (int k = 0; k < world; ++k) {
-    ksim_engine* e = engines[k];
-    KSIM_HIP(hipStreamSynchronize(e->stream));
-    if ((rc = reset_shard_state(e, st, true))) return rc;
-    rc = hmemo_init_keys(e, 1, 0, st, e->node_off);
-    if (rc) return rc;
-    HMemoArgs a = hmemo_args(e, env, 0, stride);
-    a.roff = e->node_off;
-    a.wbase = k * K;
-    a.Ktot = Kt;
-    a.gran = e0->d_ggran.p;
-    a.fail = e0->d_fail.p;
-    if (e->has_delete[0]) {
-      rc = e->hmemo.hist.ensure((size_t)K * stride);
-      if (rc) return rc;
-      a.hist = e->hmemo.hist.p;
-    }
-    args[k] = a;
+    bool planned = false;
+    if ((rc = shard_hmemo_args(engines[k], env, max_ev, K, sl.S, Kt, k * K, grp.d_ggran.p, st, &args[k], &planned))) return rc;
+    if (!planned) return KSIM_OK;  // (the fall-back resets the shards already prepared again)
+    args[k].fail = e0->d_fail.p;
+    lds = std::max(lds, engines[k]->hmemo.plan.lds);
   }
-  KSIM_HIP(hipMemcpyAsync(e0->d_hgargs.p, args.data(), sizeof(HMemoArgs) * world, hipMemcpyHostToDevice, st));
-  KSIM_HIP(hipMemsetAsync(e0->d_ggran.p, 0, sizeof(unsigned long long) * 2 * (size_t)Kt * 2, st));
+  const void* f = hmemo_kernel(hmemo_form(kHGroup, Kt, false, env.hdelay, false));
+  if (Kt > resident_cap(e0, f, lds)) return KSIM_OK;
+  KSIM_HIP(hipMemcpyAsync(grp.d_hgargs.p, args.data(), sizeof(HMemoArgs) * world, hipMemcpyHostToDevice, st));
+  KSIM_HIP(hipMemsetAsync(grp.d_ggran.p, 0, sizeof(unsigned long long) * 2 * (size_t)Kt * 2, st));
   KSIM_HIP(hipMemsetAsync(e0->d_fail.p, 0, sizeof(int), st));
   KSIM_HIP(hipStreamSynchronize(st));  // `args` is pageable
   KSIM_HIP(hipEventRecord(e0->ev0, st));
   KSIM_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const HMemoArgs* ap = e0->d_hgargs.p;
+  const HMemoArgs* ap = grp.d_hgargs.p;
   int Kk = K;
   void* params[] = {(void*)&ap, (void*)&Kk};
   const hipError_t lr = e0->coop ? hipLaunchCooperativeKernel(f, dim3(Kt), dim3(kHBlock), params, (unsigned)lds, st)
@@ -4336,22 +4309,31 @@ static int run_hmemo_group(ksim_engine* const* engines, int world, const RunEnv&
   return KSIM_OK;
 }
 
+// Engine k of the `world` given to a group entry point: rank k of that world, exchanging in this process, on engine
+// 0's device.
+static bool group_member_ok(ksim_engine* const* engines, int world, int k) {
+  const ksim_engine* e = engines[k];
+  return e && engines[0] && e->shard.world == world && e->shard.rank == k && e->shard.in_process() &&
+         e->device == engines[0]->device;
+}
+
 int ksim_shard_group_run(ksim_engine* const* engines, int world) {
   if (!engines || world < 1 || world > 16) return KSIM_EINVAL;
   ksim_engine* e0 = engines[0];
   int max_ev = 0;
   for (int k = 0; k < world; ++k) {
     ksim_engine* e = engines[k];
-    if (!e || e->shard_world != world || e->shard_rank != k || e->comm || e->xfn || e->device != e0->device ||
-        !e->d_ev[0].p)
-      return KSIM_EINVAL;
+    if (!group_member_ok(engines, world, k) || !e->d_ev[0].p) return KSIM_EINVAL;
     if (e->n_events[0] != e0->n_events[0]) return KSIM_EINVAL;  // every shard sees the same events
     if (e->report != e0->report) return KSIM_EINVAL;            // and reports, or none does: the records are merged
     max_ev = std::max(max_ev, e->n_events[0]);
   }
   KSIM_HIP(hipSetDevice(e0->device));
-  for (int k = 0; k < world; ++k) engines[k]->rep_ready = false;
-  e0->rmerge_n = -1;
+  for (int k = 0; k < world; ++k) {
+    engines[k]->rep_ready = false;
+    engines[k]->stats = RunStats{};
+  }
+  e0->shard.group.rmerge_n = -1;
   const RunEnv env = read_env();
   if (hmemo_group_eligible(engines, world, env)) {
     bool done = false;
@@ -4363,15 +4345,15 @@ int ksim_shard_group_run(ksim_engine* const* engines, int world) {
     const int rc = run_replay_group(engines, world, env, max_ev, &done);
     if (rc || done) return rc;
   }
-  for (int k = 0; k < world; ++k) engines[k]->last_kernels = "k_step";  // (named first: a failed run names its path too)
-  if (int rc = e0->d_ptrs.ensure(32)) return rc;
+  for (int k = 0; k < world; ++k) engines[k]->stats.kernels = "k_step";  // (named first: a failed run names its path too)
+  if (int rc = e0->shard.group.d_ptrs.ensure(32)) return rc;
   std::vector<unsigned long long*> ptrs(32, nullptr);
   for (int k = 0; k < world; ++k) {
-    ptrs[k] = engines[k]->d_send.p;
-    ptrs[16 + k] = engines[k]->d_recv.p;
+    ptrs[k] = engines[k]->shard.d_send.p;
+    ptrs[16 + k] = engines[k]->shard.d_recv.p;
   }
   hipStream_t st = e0->stream;
-  KSIM_HIP(hipMemcpyAsync(e0->d_ptrs.p, ptrs.data(), sizeof(unsigned long long*) * 32, hipMemcpyHostToDevice, st));
+  KSIM_HIP(hipMemcpyAsync(e0->shard.group.d_ptrs.p, ptrs.data(), sizeof(unsigned long long*) * 32, hipMemcpyHostToDevice, st));
   int rc;
   for (int k = 0; k < world; ++k) {
     KSIM_HIP(hipStreamSynchronize(engines[k]->stream));
@@ -4381,8 +4363,8 @@ int ksim_shard_group_run(ksim_engine* const* engines, int world) {
   for (int s = 0; s < max_ev; ++s) {
     for (int k = 0; k < world; ++k)
       if ((rc = shard_local(engines[k], st, nullptr, s))) return rc;
-    hipLaunchKernelGGL(k_shard_gather, dim3(1), dim3(1024), 0, st, (unsigned long long* const*)e0->d_ptrs.p,
-                       (unsigned long long* const*)(e0->d_ptrs.p + 16), world);
+    hipLaunchKernelGGL(k_shard_gather, dim3(1), dim3(1024), 0, st, (unsigned long long* const*)e0->shard.group.d_ptrs.p,
+                       (unsigned long long* const*)(e0->shard.group.d_ptrs.p + 16), world);
     KSIM_HIP(hipGetLastError());
     for (int k = 0; k < world; ++k)
       if ((rc = shard_commit(engines[k], st, nullptr, s))) return rc;
@@ -4404,50 +4386,6 @@ int ksim_engine_set_report(ksim_engine* e, int enable) {
   return KSIM_OK;
 }
 
-int ksim_engine_get_reports(ksim_engine* e, int replica, ksim_report* out, int n) {
-  if (!e || !out || replica < 0 || replica >= e->R || n < 0 || n > e->n_events[replica]) return KSIM_EINVAL;
-  if (e->shard_world > 1) return KSIM_ENOTSUP;  // one shard's nodes only: ksim_engine_get_report_parts, merged
-  if (!e->report || !e->d_rep[replica].p) return KSIM_ESTATE;
-  if (n == 0) return KSIM_OK;
-  std::vector<RepAcc> h((size_t)n);
-  KSIM_HIP(hipSetDevice(e->device));
-  KSIM_HIP(hipMemcpyAsync(h.data(), e->d_rep[replica].p, sizeof(RepAcc) * n, hipMemcpyDeviceToHost, e->stream));
-  KSIM_HIP(hipStreamSynchronize(e->stream));
-  for (int i = 0; i < n; ++i) {
-    ksim_report& o = out[i];
-    // exact fixed-point sum -> nearest double (the int128 -> double conversion rounds to nearest
-    // even; the 2^-80 scaling is exact)
-    for (int k = 0; k < 7; ++k) o.frag_bins[k] = std::ldexp((double)h[i].fx[k], -80);
-    o.used_nodes = h[i].cnt[0];
-    o.used_gpus = h[i].cnt[1];
-    o.used_gpu_milli = h[i].cnt[2];
-    o.total_gpus = e->total_gpus[replica];
-    o.arrived_gpu_milli = h[i].cnt[4];
-    o.used_cpu_milli = h[i].cnt[3];
-    o.arrived_cpu_milli = h[i].cnt[5];
-  }
-  return KSIM_OK;
-}
-
-int ksim_engine_get_power_reports(ksim_engine* e, int replica, ksim_power_report* out, int n) {
-  if (!e || !out || replica < 0 || replica >= e->R || n < 0 || n > e->n_events[replica]) return KSIM_EINVAL;
-  if (e->shard_world > 1) return KSIM_ENOTSUP;
-  if (!e->report || !e->d_rep[replica].p || !e->pw_set[replica]) return KSIM_ESTATE;
-  if (n == 0) return KSIM_OK;
-  std::vector<RepAcc> h((size_t)n);
-  KSIM_HIP(hipSetDevice(e->device));
-  KSIM_HIP(hipMemcpyAsync(h.data(), e->d_rep[replica].p, sizeof(RepAcc) * n, hipMemcpyDeviceToHost, e->stream));
-  KSIM_HIP(hipStreamSynchronize(e->stream));
-  for (int i = 0; i < n; ++i) {
-    ksim_power_report& o = out[i];
-    o.cpu_w = std::ldexp((double)h[i].fx[7], -80);
-    o.gpu_w = std::ldexp((double)h[i].fx[8], -80);
-    o.cluster_w = o.cpu_w + o.gpu_w;  // analysis.go:54 powerCPUCluster + powerGPUCluster
-    o.invalid_nodes = h[i].cnt[6];
-  }
-  return KSIM_OK;
-}
-
 // The exact records (ksim_report_part is RepAcc byte for byte; ksim_report_host.hpp turns them into reports).
 static_assert(sizeof(ksim_report_part) == sizeof(RepAcc) && offsetof(ksim_report_part, cnt) == offsetof(RepAcc, cnt),
               "ksim_report_part must match RepAcc");
@@ -4460,6 +4398,26 @@ static int fetch_parts(ksim_engine* e, const RepAcc* src, ksim_report_part* out,
   KSIM_HIP(hipMemcpyAsync(out, src, sizeof(RepAcc) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
   KSIM_HIP(hipStreamSynchronize(e->stream));
   for (int i = 0; i < n; ++i) out[i].cnt[7] = total_gpus;
+  return KSIM_OK;
+}
+
+int ksim_engine_get_reports(ksim_engine* e, int replica, ksim_report* out, int n) {
+  if (!e || !out || replica < 0 || replica >= e->R || n < 0 || n > e->n_events[replica]) return KSIM_EINVAL;
+  if (e->shard.world > 1) return KSIM_ENOTSUP;  // one shard's nodes only: ksim_engine_get_report_parts, merged
+  if (!e->report || !e->d_rep[replica].p) return KSIM_ESTATE;
+  std::vector<ksim_report_part> h((size_t)n);
+  if (int rc = fetch_parts(e, e->d_rep[replica].p, h.data(), n, e->total_gpus[replica])) return rc;
+  for (int i = 0; i < n; ++i) ksim_rep_host::part_reports(h[i], out + i, nullptr);
+  return KSIM_OK;
+}
+
+int ksim_engine_get_power_reports(ksim_engine* e, int replica, ksim_power_report* out, int n) {
+  if (!e || !out || replica < 0 || replica >= e->R || n < 0 || n > e->n_events[replica]) return KSIM_EINVAL;
+  if (e->shard.world > 1) return KSIM_ENOTSUP;
+  if (!e->report || !e->d_rep[replica].p || !e->pw_set[replica]) return KSIM_ESTATE;
+  std::vector<ksim_report_part> h((size_t)n);
+  if (int rc = fetch_parts(e, e->d_rep[replica].p, h.data(), n, e->total_gpus[replica])) return rc;
+  for (int i = 0; i < n; ++i) ksim_rep_host::part_reports(h[i], nullptr, out + i);
   return KSIM_OK;
 }
 
@@ -4482,68 +4440,62 @@ int ksim_shard_group_get_reports(ksim_engine* const* engines, int world, ksim_re
   bool ready = true, pw = true;
   for (int k = 0; k < world; ++k) {
     const ksim_engine* e = engines[k];
-    if (!e || e->shard_world != world || e->shard_rank != k || e->comm || e->xfn || e->device != e0->device) return KSIM_EINVAL;
+    if (!group_member_ok(engines, world, k)) return KSIM_EINVAL;
     ready = ready && e->report && e->rep_ready;
     pw = pw && e->pw_set[0];
     total += e->total_gpus[0];
   }
-  if (!ready || e0->rmerge_n < 0 || (power_out && !pw)) return KSIM_ESTATE;
-  if (n > e0->rmerge_n) return KSIM_EINVAL;
+  if (!ready || e0->shard.group.rmerge_n < 0 || (power_out && !pw)) return KSIM_ESTATE;
+  if (n > e0->shard.group.rmerge_n) return KSIM_EINVAL;
   std::vector<ksim_report_part> h((size_t)n);
-  if (int rc = fetch_parts(e0, e0->d_rmerge.p, h.data(), n, total)) return rc;
+  if (int rc = fetch_parts(e0, e0->shard.group.d_rmerge.p, h.data(), n, total)) return rc;
   for (int i = 0; i < n; ++i) ksim_rep_host::part_reports(h[i], out + i, power_out ? power_out + i : nullptr);
   return KSIM_OK;
 }
 
 int ksim_engine_last_report_ms(ksim_engine* e, double* ms) {
   if (!e || !ms) return KSIM_EINVAL;
-  *ms = e->last_report_ms;
+  *ms = e->stats.report_ms;
   return KSIM_OK;
 }
 
 int ksim_engine_last_run_launches(ksim_engine* e, int* launches, int* side_streams) {
   if (!e || !launches || !side_streams) return KSIM_EINVAL;
-  *launches = e->last_launches;
-  *side_streams = e->last_streams;
+  *launches = e->stats.launches;
+  *side_streams = e->stats.streams;
   return KSIM_OK;
 }
 
 int ksim_engine_last_run_kernels(ksim_engine* e, char* out, int cap) {
   if (!e || !out || cap <= 0) return KSIM_EINVAL;
-  if ((int)e->last_kernels.size() >= cap) return KSIM_ERANGE;
-  std::memcpy(out, e->last_kernels.c_str(), e->last_kernels.size() + 1);
+  const std::string& names = e->stats.kernels;
+  if ((int)names.size() >= cap) return KSIM_ERANGE;
+  std::memcpy(out, names.c_str(), names.size() + 1);
   return KSIM_OK;
 }
 
 int ksim_engine_last_run_gate(ksim_engine* e, int* gate, long long* timeouts) {
   if (!e || !gate || !timeouts) return KSIM_EINVAL;
-  *gate = e->last_gate;
+  *gate = e->stats.gate;
   *timeouts = e->gate_timeouts;
   return KSIM_OK;
 }
 
 int ksim_engine_last_run_report_overlap(ksim_engine* e, int* replicas) {
   if (!e || !replicas) return KSIM_EINVAL;
-  *replicas = e->last_ovl;
+  *replicas = e->stats.ovl;
   return KSIM_OK;
 }
 
 int ksim_engine_last_run_wgs(ksim_engine* e, int* wgs_per_replica) {
   if (!e || !wgs_per_replica) return KSIM_EINVAL;
-  *wgs_per_replica = e->run_mode == 1 ? e->bpr : e->last_K;
+  *wgs_per_replica = e->run_mode == 1 ? e->bpr : e->stats.K;
   return KSIM_OK;
 }
 
 int ksim_engine_last_run_path(ksim_engine* e, int* path) {
   if (!e || !path) return KSIM_EINVAL;
-  if (e->shard_world > 0) *path = KSIM_PATH_SHARDED;
-  else if (e->run_mode == 1 || e->last_step_path) *path = KSIM_PATH_STEP;
-  else if (e->last_rgo == e->R) *path = KSIM_PATH_RANDOM_GO;
-  else if (e->last_scan1 == e->R) *path = KSIM_PATH_SCAN1;
-  else if (e->last_memo == 0 && e->last_hmemo == 0) *path = KSIM_PATH_REPLAY;
-  else if (e->last_memo == e->R) *path = KSIM_PATH_MEMO;
-  else if (e->last_hmemo == e->R) *path = KSIM_PATH_HMEMO;
-  else *path = KSIM_PATH_MIXED;
+  *path = run_path(e->stats, e->R, e->run_mode, e->shard.on());
   return KSIM_OK;
 }
 
@@ -4578,13 +4530,13 @@ int ksim_engine_time_steps(ksim_engine* e, int n_steps, double* mean_kernel_us) 
 
 int ksim_engine_last_run_ms(ksim_engine* e, double* ms) {
   if (!e || !ms) return KSIM_EINVAL;
-  *ms = e->last_ms;
+  *ms = e->stats.ms;
   return KSIM_OK;
 }
 
 int ksim_engine_last_run_steps(ksim_engine* e, int64_t* steps) {
   if (!e || !steps) return KSIM_EINVAL;
-  *steps = e->last_steps;
+  *steps = e->stats.steps;
   return KSIM_OK;
 }
 
@@ -4630,7 +4582,7 @@ int ksim_engine_get_nodes(ksim_engine* e, int replica, ksim_node* out) {
 template <class Args, class Ensure, class... Extra>
 static int desched_plan(ksim_engine* e, double ratio, DsPlan tag, int node_bytes, Args a, Ensure ensure,
                         void (*eval)(Args, Extra...), void (*select)(Args), Extra... extra) {
-  if (e->shard_world > 0) return KSIM_ENOTSUP;
+  if (e->shard.on()) return KSIM_ENOTSUP;
   if (!e->ran) return KSIM_ESTATE;
   DeschedState& ds = e->ds;
   ds.invalidate();

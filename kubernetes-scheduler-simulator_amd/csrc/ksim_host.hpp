@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cstddef>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <utility>
@@ -86,6 +87,8 @@ struct DevHandle {
   }
 };
 using GraphExec = DevHandle<hipGraphExec_t, hipGraphExecDestroy>;
+// (The node-sharded mode's communicator is one more DevHandle: its Destroy goes through the dlopen'd RCCL, in
+// ksim_engine.hip; like every handle it leaves a null one alone.)
 
 // Created on first use: an event (hipEventDefault: a timing event, as hipEventCreate makes) and a non-blocking stream.
 struct DevEvent : DevHandle<hipEvent_t, hipEventDestroy> {
@@ -125,6 +128,49 @@ struct MappedFlags {
     if (h) (void)hipHostFree(h);
     h = d = nullptr;
     cap = 0;
+  }
+};
+
+// The exchange buffers of a world of shard processes as this rank sees them: ptr[q] is rank q's buffer, the peers'
+// opened by IPC, the own slot this rank's own allocation (never opened here, never closed).  Every other rank is
+// mapped or none is.
+struct PeerMap {
+  std::vector<unsigned long long*> ptr;  // empty: nothing mapped
+  int self = -1;
+
+  PeerMap() = default;
+  PeerMap(PeerMap&& o) noexcept : ptr(std::move(o.ptr)), self(o.self) { o.ptr.clear(); }  // one owner: no copies
+  ~PeerMap() { close(); }
+  bool mapped() const { return !ptr.empty(); }
+
+  // handles: `world` records of `stride` bytes, each beginning with a hipIpcMemHandle_t.  On a failed open the ranks
+  // opened so far are closed again, the map stays empty, and *bad / *why (nullable) name the rank and the error.
+  int open(const uint8_t* handles, size_t stride, int world, int rank, unsigned long long* own, int* bad = nullptr,
+           hipError_t* why = nullptr) {
+    close();
+    ptr.assign((size_t)world, nullptr);
+    self = rank;
+    ptr[rank] = own;
+    for (int q = 0; q < world; ++q) {
+      if (q == rank) continue;
+      hipIpcMemHandle_t h;
+      std::memcpy(&h, handles + (size_t)q * stride, sizeof h);
+      void* p = nullptr;
+      const hipError_t r = hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess);
+      if (r != hipSuccess) {
+        if (bad) *bad = q;
+        if (why) *why = r;
+        close();  // (the ranks past q are still null)
+        return KSIM_EHIP;
+      }
+      ptr[q] = reinterpret_cast<unsigned long long*>(p);
+    }
+    return KSIM_OK;
+  }
+  void close() {
+    for (int q = 0; q < (int)ptr.size(); ++q)
+      if (q != self && ptr[q]) (void)hipIpcCloseMemHandle(ptr[q]);
+    ptr.clear();
   }
 };
 

@@ -1,5 +1,6 @@
-// The owning handles of ksim_host.hpp (DevBuf, DevEvent, DevStream, MappedFlags, GraphExec) on the CPU: malloc-backed
-// stand-ins for the HIP calls they make count the live objects of each kind and fail the k-th call on request.
+// The owning handles of ksim_host.hpp (DevBuf, DevEvent, DevStream, MappedFlags, GraphExec, PeerMap, the communicator's
+// DevHandle) on the CPU: malloc-backed stand-ins for the HIP calls they make count the live objects of each kind and
+// fail the k-th call on request.
 // Exit status 0 and a line of tallies per check when everything holds; the first broken expectation aborts.
 #include <cstdio>
 #include <cstdlib>
@@ -38,7 +39,14 @@ struct Tally {
   long mallocs = 0, ext_mallocs = 0, frees = 0, copies = 0, copied_bytes = 0, memsets = 0, event_creates = 0,
        stream_creates = 0, host_mallocs = 0;
   size_t last_bytes = 0;
-  bool none_live() const { return blocks.empty() && host.empty() && events.empty() && streams.empty() && graphs.empty(); }
+  std::set<void*> ipc;                     // live IPC mappings
+  std::set<struct FakeComm*> comms;        // live communicators
+  std::vector<int> ipc_ranks;              // the rank each open named, in call order
+  long ipc_opens = 0, ipc_closes = 0, comm_destroys = 0;
+  bool none_live() const {
+    return blocks.empty() && host.empty() && events.empty() && streams.empty() && graphs.empty() && ipc.empty() &&
+           comms.empty();
+  }
 };
 static Tally T;
 
@@ -126,6 +134,32 @@ static hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned) {
   if (injected()) return hipErrorOutOfMemory;
   CHECK(T.host.count(h) == 1);
   *d = h;
+  return hipSuccess;
+}
+// IPC: a handle names its rank in its first byte; an opened mapping is a block of its own, closed once
+struct hipIpcMemHandle_t { char reserved[64]; };
+constexpr unsigned hipIpcMemLazyEnablePeerAccess = 1;
+static hipError_t hipIpcOpenMemHandle(void** p, hipIpcMemHandle_t h, unsigned flags) {
+  if (injected()) return hipErrorOutOfMemory;
+  CHECK(flags == hipIpcMemLazyEnablePeerAccess);
+  ++T.ipc_opens;
+  T.ipc_ranks.push_back(h.reserved[0]);
+  T.ipc.insert(*p = garbage(8));
+  return hipSuccess;
+}
+static hipError_t hipIpcCloseMemHandle(void* p) {
+  CHECK(T.ipc.erase(p) == 1);  // closed once, and only what was opened: never the own buffer
+  ++T.ipc_closes;
+  std::free(p);
+  return hipSuccess;
+}
+// the communicator's stand-in: its destroyer counts
+typedef struct FakeComm* fakeComm_t;
+struct FakeComm { int rank; };
+hipError_t fake_comm_destroy(fakeComm_t c) {
+  CHECK(T.comms.erase(c) == 1);
+  ++T.comm_destroys;
+  delete c;
   return hipSuccess;
 }
 hipError_t hipGraphExecDestroy(hipGraphExec_t g) {
@@ -337,11 +371,96 @@ static void check_all_or_nothing() {
               total, blocks);
 }
 
+// PeerMap over a world of 4: every rank but the own one is opened, or none stays open.
+static void check_peer_map() {
+  constexpr int kWorld = 4;
+  constexpr size_t kStride = 128;  // a record is longer than the IPC handle it begins with
+  std::vector<uint8_t> handles(kWorld * kStride, 0);
+  for (int q = 0; q < kWorld; ++q) handles[q * kStride] = (uint8_t)q;
+  DevBuf<unsigned long long> own;
+  CHECK(own.alloc(16, hipDeviceMallocUncached) == KSIM_OK);
+  long failures = 0;
+  for (int rank = 0; rank < kWorld; ++rank) {
+    for (int k = 1; k <= kWorld - 1; ++k) {  // the k-th open fails
+      PeerMap m;
+      const long o0 = T.ipc_opens, c0 = T.ipc_closes;
+      T.ipc_ranks.clear();
+      T.fail_at = T.calls + k;
+      int bad = -1;
+      hipError_t why = hipSuccess;
+      CHECK(m.open(handles.data(), kStride, kWorld, rank, own.p, &bad, &why) == KSIM_EHIP);
+      T.fail_at = 0;
+      CHECK(T.ipc_opens == o0 + k - 1 && T.ipc_closes == c0 + k - 1);  // exactly the opened ones are closed
+      CHECK(T.ipc.empty() && !m.mapped() && m.ptr.empty());             // the map is empty afterwards
+      CHECK(T.blocks.count(own.p) == 1);                                 // the own buffer is untouched
+      CHECK(why == hipErrorOutOfMemory && bad != rank && bad == (k - 1 < rank ? k - 1 : k));  // the k-th other rank
+      for (int r : T.ipc_ranks) CHECK(r != rank);
+      ++failures;
+    }
+    const long c0 = T.ipc_closes;
+    {
+      PeerMap m;
+      T.ipc_ranks.clear();
+      CHECK(m.open(handles.data(), kStride, kWorld, rank, own.p) == KSIM_OK && m.mapped());
+      CHECK((int)m.ptr.size() == kWorld && m.ptr[rank] == own.p && (int)T.ipc.size() == kWorld - 1);
+      CHECK((int)T.ipc_ranks.size() == kWorld - 1);
+      for (int q = 0; q < kWorld; ++q) CHECK(q == rank || T.ipc.count(m.ptr[q]) == 1);
+      PeerMap moved(std::move(m));
+      CHECK(!m.mapped() && moved.mapped() && moved.ptr[rank] == own.p && T.ipc_closes == c0);
+      {
+        PeerMap gone(std::move(moved));  // dies here: closes world - 1, never the own slot
+      }
+      CHECK(T.ipc_closes == c0 + kWorld - 1 && T.ipc.empty());
+    }  // m and moved die moved-from: they close nothing
+    CHECK(T.ipc_closes == c0 + kWorld - 1 && T.blocks.count(own.p) == 1);
+  }
+  own.release();
+  CHECK(T.none_live());
+  std::printf("peermap: world=%d failures_injected=%ld opens=%ld closes=%ld live=0\n", kWorld, failures, T.ipc_opens,
+              T.ipc_closes);
+}
+
+// The communicator's owner is a DevHandle over the library's destroyer: one destroy per communicator held, none for null.
+static void check_comm_owner() {
+  using Comm = DevHandle<fakeComm_t, fake_comm_destroy>;
+  const auto fresh = [](int rank) {
+    fakeComm_t c = new FakeComm{rank};
+    T.comms.insert(c);
+    return c;
+  };
+  {
+    Comm none;  // never initialised (an in-process group's shard): nothing to destroy
+    CHECK(!none);
+  }
+  CHECK(T.comm_destroys == 0);
+  {
+    Comm c;
+    c.h = fresh(0);  // as ncclCommInitRank(&comm.h, ...) leaves it
+    Comm moved(std::move(c));
+    CHECK(!c && moved && T.comms.size() == 1);
+    Comm failed;
+    failed.h = nullptr;  // a failed init puts the null back
+  }
+  CHECK(T.comm_destroys == 1 && T.comms.empty());
+  {
+    Comm a, b;
+    a.h = fresh(1);
+    b.h = fresh(2);
+    a.reset();
+    a.reset();  // already null
+    CHECK(T.comm_destroys == 2 && T.comms.size() == 1);
+  }
+  CHECK(T.comm_destroys == 3 && T.none_live());
+  std::printf("comm: held=3 destroys=%ld null_destroys=0 live=0\n", T.comm_destroys);
+}
+
 int main() {
   check_devbuf();
   check_move();
   check_event_stream_flags_graph();
   check_all_or_nothing();
+  check_peer_map();
+  check_comm_owner();
   CHECK(T.none_live());
   std::printf("ok\n");
   return 0;

@@ -141,3 +141,52 @@ def test_run_plan(world, case, monkeypatch):
             s = state[i]
             assert s.cpu_alloc_milli - s.cpu_used_milli == cpu_left and s.pods_used == pods, (r, i)
             assert [1000 - s.gpu_used_milli[g] if g < s.gpu_count else 0 for g in range(8)] == gl, (r, i)
+
+
+# Two of CASES with the same replica count and engine arguments, one after the other on the same engine.  (CASES has
+# no k_random_go-only case, so no pair ends on one after a memo case: "f-random-go-last" runs k_scan1_mix beside it and
+# is the only case of three replicas.)
+PAIRS = [("a-fgd-beside-mix", "d-split-fgd"), ("d-split-fgd", "a-fgd-beside-mix"), ("g-round-robin-1", "g-round-robin-2")]
+
+
+def set_case(eng, world, c, monkeypatch):
+    """Case c's environment, policies, hints and events on an engine that may have run another case before."""
+    for var in ("KSIM_VARIANT", "KSIM_TEST", "KSIM_SIDE_STREAMS", "KSIM_PROFILE", "KSIM_GROUP_TIMES"):
+        monkeypatch.delenv(var, raising=False)
+    for var, val in c.get("env", {}).items():
+        monkeypatch.setenv(var, val)
+    for r, spec in enumerate(c["reps"]):
+        assert not (spec.get("go") or spec.get("deletes") or spec["policy"].startswith("PWR"))  # (none of PAIRS)
+        eng.set_policy(r, spec["policy"], seed=SEED)
+        eng.set_replica_wgs(r, spec.get("wgs", 0))
+        eng.load_events(r, world["rp"].events, spec["n_ev"])
+
+
+@pytest.mark.parametrize("first,second", PAIRS, ids=["%s-then-%s" % (a[0], b[0]) for a, b in PAIRS])
+def test_two_runs_report_each_run_alone(world, first, second, monkeypatch):
+    assert len(CASES[first]["reps"]) == len(CASES[second]["reps"])
+    assert CASES[first].get("engine") == CASES[second].get("engine") and not CASES[first].get("report")
+    trace, rp = world["trace"], world["rp"]
+    arr, n = world["typical"]
+    R = len(CASES[first]["reps"])
+    eng = ksim.Engine(trace.num_nodes, R, **CASES[first].get("engine", dict(wgs_per_replica=1)))
+    seen, got = {}, {}
+    try:
+        for r in range(R):
+            eng.set_nodes(r, rp.nodes)
+            eng.set_typical(r, arr, n)
+        for case in (first, second):
+            set_case(eng, world, CASES[case], monkeypatch)
+            eng.run()
+            seen[case] = (eng.last_run_kernels(), eng.last_run_launches(), eng.last_run_wgs(), eng.last_run_path(),
+                          eng.last_run_gate()[0], eng.last_run_report_overlap())
+            got[case] = [eng.results(r) for r in range(R)]
+    finally:
+        eng.close()
+    print("two runs %s, %s: %r" % (first, second, seen))
+    for case in (first, second):
+        assert seen[case] == CASES[case]["want"], case
+        for r, spec in enumerate(CASES[case]["reps"]):
+            want, _ = oracle(world, spec)
+            bad = [i for i, (a, b) in enumerate(zip(got[case][r], want)) if a != b]
+            assert len(got[case][r]) == len(want) and not bad, (case, r, spec["policy"], bad[:1])

@@ -68,6 +68,37 @@ def test_group_fgd_step_path_still_equal(default_trace, world, monkeypatch):
     assert got == unsharded(default_trace, rp.nodes, rp.events, n_ev, "FGD")
 
 
+def test_group_run_twice_reports_each_run_alone(default_trace, monkeypatch):
+    # One group, two runs: k_hmemo's sharded launch, then (KSIM_VARIANT=shard_hmemo=0) the per-pod k_step path.  After
+    # each run the getters of every engine of the group report that run alone: the second run has no width, whatever
+    # the first one had.
+    monkeypatch.delenv("KSIM_VARIANT", raising=False)
+    rp = default_trace.replay(seed=43)
+    nodes = helpers.subset_nodes(rp, list(range(0, default_trace.num_nodes, 5)))
+    n_ev = 300
+    g = SH.ShardGroup(nodes, default_trace.typical(), 2)
+    try:
+        g.load_events(rp.events, n_ev)
+        g.run()
+        first = [(e.last_run_kernels(), e.last_run_wgs(), e.last_run_path()) for e in g.engines]
+        got1 = g.results()
+        monkeypatch.setenv("KSIM_VARIANT", "shard_hmemo=0")
+        g.run()
+        second = [(e.last_run_kernels(), e.last_run_wgs(), e.last_run_path()) for e in g.engines]
+        got2 = g.results()
+    finally:
+        g.close()
+    monkeypatch.delenv("KSIM_VARIANT", raising=False)
+    print("group run twice:", first, second)
+    for kernels, wgs, path in first:
+        assert kernels == ["k_hmemo_group"] and wgs >= 1 and path == "sharded"
+    for kernels, wgs, path in second:
+        assert kernels == ["k_step"] and wgs == 0 and path == "sharded"
+    want = unsharded(default_trace, nodes, rp.events, n_ev, "FGD")
+    assert got1 == want
+    assert got2 == want
+
+
 @pytest.mark.parametrize("name,pol,sel", POLICIES, ids=[p[0] for p in POLICIES])
 def test_group_all_policies_vs_oracle(default_trace, name, pol, sel):
     rp = default_trace.replay(seed=7)
