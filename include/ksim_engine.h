@@ -428,11 +428,11 @@ int  ksim_engine_last_run_path(ksim_engine* e, int* path);
  * events.  The victims are rescheduled by replaying the stream extended with their deletions and
  * re-creations (ksim/desched.py).  Order contract where the reference's order is a Go map's: pods of a node
  * in ascending creation-event index, nodes of equal priority by name_rank (DESIGN.md "Descheduling").
- *   KSIM_EINVAL   bad policy, ratio < 0 or NaN         KSIM_ENOTSUP  node-sharded engine
+ *   KSIM_EINVAL   bad policy, ratio < 0 or NaN         KSIM_ENODEV   no gfx950 device
  *   KSIM_ESTATE   no completed run since the last set_nodes / set_typical / load_events
- *   KSIM_ENODEV   no gfx950 device
  * ksim_engine_get_victims: replica's victims in eviction order into out[cap]; *n_out their number (set even
- * when cap is too small: KSIM_ERANGE), *budget_out (nullable) the budget.  KSIM_ESTATE before a plan.
+ * when cap is too small: KSIM_ERANGE), *budget_out (nullable) the budget.  KSIM_ESTATE before a plan;
+ * KSIM_ENOTSUP  node-sharded engine (its list is a part: "Descheduling on a node-sharded cluster" below).
  * ksim_engine_last_deschedule_ms: device time of the last plan, its host step between the kernels included. */
 enum ksim_desched_policy { KSIM_DESCHED_FRAG_ONE_POD = 0, KSIM_DESCHED_FRAG_MULTI_POD = 1 };
 typedef struct {
@@ -456,8 +456,9 @@ int  ksim_engine_last_deschedule_ms(ksim_engine* e, double* ms);
  * the least cosine similarity between [CPU left, total milli-GPU left] of the node after NodeResource.Add and
  * the pod's [MilliCpu, MilliGpu x GpuNumber] is the victim: 0 <= similarity < 1 only, the lowest creation-event
  * index among equals, one victim a node, until the budget is used.  A node without a victim uses no budget.
- *   KSIM_EINVAL   ratio < 0 or NaN, a negative bar       KSIM_ENOTSUP  node-sharded engine
+ *   KSIM_EINVAL   ratio < 0 or NaN, a negative bar
  *   KSIM_ESTATE   no completed run                        KSIM_ENODEV   no gfx950 device
+ * ksim_engine_get_cos_victims on a node-sharded engine: KSIM_ENOTSUP  node-sharded engine (its list is a part).
  * An engine holds one plan: after ksim_engine_deschedule_cossim, ksim_engine_get_victims returns KSIM_ESTATE,
  * and ksim_engine_get_cos_victims does after ksim_engine_deschedule.  ksim_engine_get_cos_victims follows
  * ksim_engine_get_victims; ksim_engine_last_deschedule_ms reports the last plan of either kind. */
@@ -472,6 +473,40 @@ typedef struct {
 int  ksim_engine_deschedule_cossim(ksim_engine* e, double ratio, int64_t cpu_bar_milli, int64_t gpu_bar_milli);
 int  ksim_engine_get_cos_victims(ksim_engine* e, int replica, ksim_cos_victim* out, int cap, int* n_out,
                                  int* budget_out);
+
+/* Descheduling on a node-sharded cluster.  In all three policies a node's evictions depend only on its own pods and
+ * its own priority history; the nodes meet only in the visiting order and in the budget.  So every shard plans the
+ * pods bound to its own nodes (ksim_engine_deschedule / ksim_engine_deschedule_cossim on a shard, after its run: its
+ * PART), and the cluster's plan is the merge of the parts by the key of the visiting order -- (frag_before
+ * descending, node rank ascending), for cosSim (gpu_left_milli descending, node rank ascending) -- cut at
+ * ceil(ratio * the bound pods of all shards).  A shard does not know that budget: its select is capped at
+ * ceil(ratio * creation events of its stream), which is never less, so a part may be longer than the cluster's plan
+ * but always holds every entry the merge takes from it.  `node` in a part and in a merged list is the global rank.
+ *   ksim_engine_get_victim_part / _cos_victim_part   the engine's own list (replica 0) and *bound_out (nullable) the
+ *       pods bound on its nodes; on an unsharded engine the plan itself.  KSIM_ESTATE without a plan of that kind,
+ *       KSIM_ERANGE (with *n_out set) when cap is too small.  The bytes are what travels between shard processes.
+ *   ksim_desched_merge / ksim_cos_merge   host only (no device needed): the merge of parts[k][0..n[k]) with bound[k],
+ *       k < world, at `ratio` into out[cap]; *n_out, *budget_out (nullable) and KSIM_ERANGE as the getters.
+ *       KSIM_EINVAL: a null argument, world outside 1..16, a negative count or bound, ratio < 0 or NaN.
+ *   ksim_shard_group_deschedule / _deschedule_cossim   an in-process group (arguments as ksim_shard_group_run's)
+ *       after its run: every shard's part, the bound counts summed, the budget, and the merge on the device
+ *       (k_victim_merge).  ksim_engine_last_deschedule_ms of engine 0 spans the parts and the merge.
+ *   ksim_shard_group_get_victims / _get_cos_victims   the merged list of the last group plan.  KSIM_EINVAL for engines
+ *       that are not that group; KSIM_ESTATE before a completed group plan of that kind, or after anything that
+ *       dropped or replaced a shard's plan (a run, load_events, a plan of its own). */
+int  ksim_engine_get_victim_part(ksim_engine* e, ksim_victim* out, int cap, int* n_out, int64_t* bound_out);
+int  ksim_engine_get_cos_victim_part(ksim_engine* e, ksim_cos_victim* out, int cap, int* n_out, int64_t* bound_out);
+int  ksim_desched_merge(const ksim_victim* const* parts, const int* n, const int64_t* bound, int world, double ratio,
+                        ksim_victim* out, int cap, int* n_out, int* budget_out);
+int  ksim_cos_merge(const ksim_cos_victim* const* parts, const int* n, const int64_t* bound, int world, double ratio,
+                    ksim_cos_victim* out, int cap, int* n_out, int* budget_out);
+int  ksim_shard_group_deschedule(ksim_engine* const* engines, int world, int policy, double ratio);
+int  ksim_shard_group_deschedule_cossim(ksim_engine* const* engines, int world, double ratio, int64_t cpu_bar_milli,
+                                        int64_t gpu_bar_milli);
+int  ksim_shard_group_get_victims(ksim_engine* const* engines, int world, ksim_victim* out, int cap, int* n_out,
+                                  int* budget_out);
+int  ksim_shard_group_get_cos_victims(ksim_engine* const* engines, int world, ksim_cos_victim* out, int cap,
+                                      int* n_out, int* budget_out);
 
 #ifdef __cplusplus
 }

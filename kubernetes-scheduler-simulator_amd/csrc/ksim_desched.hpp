@@ -11,7 +11,9 @@
 //   k_desched_select  one workgroup per replica: the pop / pick / re-key loop of the policy over those
 //                     values, victims in eviction order.
 // The cosSim policy (:49-92; the victim of one node: findVictimPodOnCosSim, deschedule_utils.go:15-45) shares
-// k_desched_mark and has k_cos_eval and k_cos_select of its own, at the end of this file.  The host side is one
+// k_desched_mark and has k_cos_eval and k_cos_select of its own, after the frag kernels.  On a node-sharded engine
+// the same kernels plan the pods on the shard's own nodes (the ownership rule, eval_bound_node), and k_victim_merge,
+// at the end of this file, merges the shards' lists into the cluster's plan.  The host side is one
 // driver for all policies: desched_plan in ksim_engine.hip, its arithmetic in ksim_desched_host.hpp.
 // The rescheduling itself is the ordinary replay of the extended event stream (ksim/desched.py).
 // No kernel here waits for another workgroup, and nothing is on the per-pod path.
@@ -103,7 +105,7 @@ KSIM_HD double cos_similarity(int cpuL, const int (&gl)[kMaxGpu], int gpu_cnt, i
 struct __align__(16) EvalRec {
   double f_node;    // F(final state of the node)
   double f_after;   // F(node + pod), valid when ok
-  int32_t node;
+  int32_t node;     // local index
   int32_t gpu_mask;
   int32_t ok;       // Add succeeded
   int32_t pad;
@@ -127,6 +129,8 @@ struct PlanArgs {          // what the kernels of every policy take
   int32_t* n_vict;         // [R]
   uint8_t* tab;            // [R][tab_stride(N, its bytes per node)] the select kernel's tables beyond LDS, else null
   int N;
+  int node_off;            // a node-sharded engine: the global rank of its local node 0 (else 0) ...
+  int sharded;             // ... and 1: results carry global ranks, and only the owner of a node plans its pods
 };
 
 struct DsArgs : PlanArgs {
@@ -148,20 +152,26 @@ __global__ __launch_bounds__(kEvalBlock) void k_desched_mark(PlanArgs a) {
 }
 
 // The opening of both eval kernels, for event e (< n_events) of replica r: returns whether its pod is still bound
-// and, when the result record validates, calls body(node, its unpacked GPU-left array) inside the two tests, as the
+// and, when the result record validates, calls body(local index, node, its GPU-left array) inside the two tests, as the
 // kernels had it inline (the compiler's output is the same).  The record is validated before it indexes anything:
 // the node index before the node is loaded, the mask against the node's GPU count before anything uses it.
+// The ownership rule of a node-sharded engine (report_delta_event's): results carry global ranks, local = rank -
+// node_off indexes rp.nodes, rp.cap and the select kernels' tables, and a pod counts as bound, and is a candidate,
+// only where 0 <= local < N -- the other shards hold a provisional record of that step.  Unsharded, node_off is 0
+// and every pod that passes the three tests is bound, as it always was.  body(local, node, GPU-left array).
 template <class F>
 __device__ __forceinline__ bool eval_bound_node(const PlanArgs& a, const ReplicaDev& rp, int r, int e, const PodDev& p,
                                                 const ResultDev& res, F&& body) {
-  const bool bound = !(p.flags & kPodDelete) && res.status == ST_OK && !a.gone[a.eoff[r] + e];
-  if (bound && res.node >= 0 && res.node < a.N && res.gpu_mask >= 0) {
-    const NodeV n = load_node(rp.nodes + res.node);
+  const int local = res.node >= 0 ? res.node - a.node_off : -1;
+  const bool owned = local >= 0 && local < a.N;
+  const bool bound = !(p.flags & kPodDelete) && res.status == ST_OK && !a.gone[a.eoff[r] + e] && (owned || !a.sharded);
+  if (bound && owned && res.gpu_mask >= 0) {
+    const NodeV n = load_node(rp.nodes + local);
     const int cnt = n.gpu_cnt();
     if (cnt <= kMaxGpu && ((unsigned)res.gpu_mask >> cnt) == 0u) {
       int gl[kMaxGpu];
       unpack_gl(n, gl);
-      body(n, gl);
+      body(local, n, gl);
     }
   }
   return bound;
@@ -198,11 +208,11 @@ __global__ __launch_bounds__(kEvalBlock) void k_desched_eval(DsArgs a, const Typ
     out.pad = 0;
     const PodDev p = rp.ev[e];
     const ResultDev res = rp.res[e];
-    bound = eval_bound_node(a, rp, r, e, p, res, [&](const NodeV& n, const int (&gl)[kMaxGpu]) {
+    bound = eval_bound_node(a, rp, r, e, p, res, [&](int local, const NodeV& n, const int (&gl)[kMaxGpu]) {
       const int cnt = n.gpu_cnt();
       const uint32_t tb = 1u << n.gpu_type();
-      const int cap = rp.cap[res.node];
-      out.node = res.node;
+      const int cap = rp.cap[local];
+      out.node = local;
       out.gpu_mask = res.gpu_mask;
       if (rp.typed) {
         out.f_node = frag_F<true>(n.cpu_left, gl, tb, s_tp, rp.ncpu, rp.nt);
@@ -379,7 +389,7 @@ __global__ __launch_bounds__(kSelBlock) void k_desched_select(DsArgs a) {
         const EvalRec c = ev[e];
         ksim_victim v;
         v.event = e;
-        v.node = c.node;
+        v.node = c.node + a.node_off;  // the global rank, as a shard's results carry it
         v.gpu_mask = c.gpu_mask;
         v.reserved = 0;
         v.score = (long long)(pk >> 32);
@@ -408,7 +418,7 @@ __global__ __launch_bounds__(kSelBlock) void k_desched_select(DsArgs a) {
 // What k_cos_eval leaves per event (16 B).  node < 0: not a bound pod, or a record that does not validate.
 struct __align__(16) CosRec {
   double sim;  // cos_similarity: -1 when the reference skips the pod
-  int32_t node;
+  int32_t node;  // local index
   int32_t gpu_mask;
 };
 static_assert(sizeof(CosRec) == 16, "CosRec layout");
@@ -442,10 +452,10 @@ __global__ __launch_bounds__(kEvalBlock) void k_cos_eval(CosArgs a) {
     out.gpu_mask = 0;
     const PodDev p = rp.ev[e];
     const ResultDev res = rp.res[e];
-    bound = eval_bound_node(a, rp, r, e, p, res, [&](const NodeV& n, const int (&gl)[kMaxGpu]) {
-      out.node = res.node;
+    bound = eval_bound_node(a, rp, r, e, p, res, [&](int local, const NodeV& n, const int (&gl)[kMaxGpu]) {
+      out.node = local;
       out.gpu_mask = res.gpu_mask;
-      out.sim = cos_similarity(n.cpu_left, gl, n.gpu_cnt(), rp.cap[res.node], p.cpu_nz, p.milli, p.num,
+      out.sim = cos_similarity(n.cpu_left, gl, n.gpu_cnt(), rp.cap[local], p.cpu_nz, p.milli, p.num,
                                (unsigned)res.gpu_mask);
     });
     a.rec[a.eoff[r] + e] = out;
@@ -541,7 +551,7 @@ __global__ __launch_bounds__(kSelBlock) void k_cos_select(CosArgs a) {
     const CosRec c = rec[e];
     ksim_cos_victim v;
     v.event = e;
-    v.node = i;
+    v.node = i + a.node_off;
     v.gpu_mask = c.gpu_mask;
     v.reserved = 0;
     v.gpu_left_milli = (long long)(kMaxGpu * kMilli) - (long long)(skey[k] >> 32);
@@ -549,6 +559,82 @@ __global__ __launch_bounds__(kSelBlock) void k_cos_select(CosArgs a) {
     vict[k] = v;
   }
   if (tid == 0) a.n_vict[r] = nv;
+}
+
+// ---- the merge of the shards' plans (node-sharded cluster) -------------------------------------------------------
+// A node's pops depend only on its own pods and its own priority history, so the cluster's victim list is the merge of
+// the shards' lists by the key the select kernels walk in -- (frag_before descending, global rank ascending), for
+// cosSim (gpu_left_milli descending, rank ascending) -- cut at the cluster's budget.  Every shard's list is sorted by
+// that key and the key is unique (DESIGN.md "Descheduling on shards").
+
+struct MergeKey {
+  unsigned long long prio;  // higher first
+  unsigned rank;            // then lower first
+};
+__host__ __device__ inline bool key_before(const MergeKey& x, const MergeKey& y) {
+  return x.prio > y.prio || (x.prio == y.prio && x.rank < y.rank);
+}
+// frag_before is a non-negative double (its bits order as an integer, + 0.0 folds a negative zero); gpu_left_milli is
+// at most 8000 and never negative.
+__host__ __device__ inline MergeKey merge_key(const ksim_victim& v) {
+  return MergeKey{__builtin_bit_cast(unsigned long long, v.frag_before + 0.0), (unsigned)v.node};
+}
+__host__ __device__ inline MergeKey merge_key(const ksim_cos_victim& v) {
+  return MergeKey{(unsigned long long)v.gpu_left_milli, (unsigned)v.node};
+}
+
+constexpr int kMergeWorld = 16;
+constexpr int kMergeBlock = 256;
+
+template <class V>
+struct MergeArgs {
+  const V* part[kMergeWorld];  // each shard's list, sorted by the key
+  int n[kMergeWorld];          // its length, clamped to its buffer on the host and here to >= 0
+  int world;
+  int budget;                  // the cluster's
+  V* out;                      // [out_cap] the merged list
+  int out_cap;
+  int32_t* n_out;              // min(budget, sum of n), at most out_cap
+};
+
+// grid ceil(sum n / kMergeBlock): one thread per input entry.  The entry at position i of shard k counts, in every
+// other shard's list, the entries with a strictly better key (a binary search: the lists are sorted and the keys
+// unique); i plus those counts is its place in the merged order, and it stores its record there when that is inside
+// the budget.  Plain stores to distinct places; no workgroup waits for another; every loop is bounded (world <= 16,
+// a search halves an int range: <= 32 steps).
+// The arguments sit in device memory (a table indexed by the shard: plain loads, no copy of it per thread).
+template <class V>
+__global__ __launch_bounds__(kMergeBlock) void k_victim_merge(const MergeArgs<V>* __restrict__ ap) {
+  const MergeArgs<V>& a = *ap;
+  const int world = min(max(a.world, 0), kMergeWorld);
+  long long t = (long long)blockIdx.x * kMergeBlock + (long long)threadIdx.x;
+  long long total = 0;
+  int k = -1, i = 0;
+  for (int j = 0; j < world; ++j) {
+    const int nj = max(a.n[j], 0);
+    if (k < 0 && t >= total && t < total + nj) {
+      k = j;
+      i = (int)(t - total);
+    }
+    total += nj;
+  }
+  const long long cut = min(min((long long)max(a.budget, 0), total), (long long)max(a.out_cap, 0));
+  if (t == 0) *a.n_out = (int32_t)cut;
+  if (k < 0) return;
+  const V mine = a.part[k][i];
+  const MergeKey key = merge_key(mine);
+  long long pos = i;
+  for (int j = 0; j < world; ++j) {
+    if (j == k) continue;
+    int lo = 0, hi = max(a.n[j], 0);  // the first entry of list j that is not before `mine`
+    for (int s = 0; s < 32 && lo < hi; ++s) {
+      const int mid = lo + ((hi - lo) >> 1);
+      if (key_before(merge_key(a.part[j][mid]), key)) lo = mid + 1;
+      else hi = mid;
+    }
+    pos += lo;
+  }
+  if (pos < cut) a.out[pos] = mine;
 }
 
 }  // namespace ksim_ds

@@ -1779,6 +1779,7 @@ __global__ __launch_bounds__(64) void k_reserve(ReplicaDev* reps, const TypDev* 
 #include "ksim_host.hpp"
 #include "ksim_report_host.hpp"
 #include "ksim_desched_host.hpp"
+#include "ksim_desched_merge_host.hpp"
 #include "ksim_run_host.hpp"
 
 // ---------------------------------------------------------------------------
@@ -1826,7 +1827,10 @@ struct DeschedState {  // the descheduling plan (desched_plan), made from the re
                        // last completed run: an engine holds one, of one policy
   DsPlan plan = kDsNone;
   std::vector<long long> eoff;      // [R + 1] each replica's offset in the per-event buffers
-  std::vector<int32_t> budget, nv;  // [R]
+  std::vector<int32_t> budget, nv;  // [R] (on a shard, budget is the cap of its select: desched_plan)
+  std::vector<int32_t> bound;       // [R] the pods bound (on a shard: to its own nodes)
+  double ratio = 0;                 // the plan's ratio
+  unsigned long long gen = 0;       // counts the plans made and dropped (a group's merged list names the plans it read)
   DevBuf<long long> d_eoff;
   DevBuf<uint8_t> gone;
   DevBuf<int32_t> cnt;              // [3][R] bound pods, budget, victims
@@ -1838,7 +1842,7 @@ struct DeschedState {  // the descheduling plan (desched_plan), made from the re
   DevBuf<ksim_cos_victim> cvict;
   DevEvent ev0, ev1;
   double last_ms = 0;
-  void invalidate() { plan = kDsNone; }
+  void invalidate() { plan = kDsNone, ++gen; }
 };
 
 static hipError_t destroy_comm(ncclComm_t c);  // through the dlopen'd RCCL
@@ -1872,6 +1876,15 @@ struct ShardState {  // a node-sharded cluster's shard (ksim_engine_set_shard): 
     DevBuf<int> d_rglist;
     DevBuf<RepAcc> d_rmerge;                // the merged report records (k_report_merge)
     int rmerge_n = -1;  // events they hold (-1: no group run with the report on since the events were loaded)
+    // the merged descheduling plan (k_victim_merge; ksim_shard_group_deschedule): the list of the policy kind
+    // `dplan`, its length and the cluster's budget, and the plan of every shard it was merged from
+    DevBuf<ksim_victim> d_vmerge;
+    DevBuf<ksim_cos_victim> d_cmerge;
+    DevBuf<int32_t> d_nmerge;
+    DevBuf<uint8_t> d_margs;  // k_victim_merge's arguments
+    DsPlan dplan = kDsNone;
+    int dmerge_n = 0, dbudget = 0;
+    std::vector<unsigned long long> dgen;
   } group;
 
   // the entry points decide through these (ksim_run_host.hpp)
@@ -1927,6 +1940,7 @@ struct ksim_engine {
   std::vector<DevBuf<ResultDev>> d_res;
   std::vector<int> n_events;
   std::vector<char> has_delete;  // the replica's stream has deletion events (k_replay keeps a bind history)
+  std::vector<int> n_create;     // its creation events (a shard's descheduling cap)
   // k_memo (memoised FGD replay): per replica the distinct pod requests of its creation events
   // (PodDev.pad = class id) and how many events each has
   std::vector<std::vector<PodDev>> h_cls;
@@ -2722,7 +2736,7 @@ static int init_replicas(ksim_engine* e) {
   const size_t n = (size_t)e->N;
   const auto per_replica = [R](auto&... v) { (v.resize(R), ...); };  // empty buffers, zero counts
   per_replica(e->reps, e->h_nodes, e->h_rec, e->h_cls, e->h_tp, e->h_cls_n, e->h_ev_cls, e->go_state, e->d_ev, e->d_res,
-              e->d_snap, e->d_prev, e->d_rep, e->n_events, e->has_delete, e->wgs_hint, e->nt, e->total_gpus, e->pw_set);
+              e->d_snap, e->d_prev, e->d_rep, e->n_events, e->has_delete, e->n_create, e->wgs_hint, e->nt, e->total_gpus, e->pw_set);
   for (int r = 0; r < R; ++r) {
     ReplicaDev& rp = e->reps[r];
     std::memset(&rp, 0, sizeof rp);
@@ -3153,6 +3167,8 @@ int ksim_engine_load_events(ksim_engine* e, int replica, const ksim_pod* events,
   if (n > 0) KSIM_HIP(hipMemcpyAsync(ev.p, h.data(), sizeof(PodDev) * n, hipMemcpyHostToDevice, e->stream));
   e->has_delete[replica] = false;
   for (int i = 0; i < n; ++i) e->has_delete[replica] = e->has_delete[replica] || events[i].is_delete;
+  e->n_create[replica] = 0;
+  for (int i = 0; i < n; ++i) e->n_create[replica] += events[i].is_delete ? 0 : 1;
   rc = alloc_report(e, replica);
   if (rc) return rc;
   rc = upload_reps(e);
@@ -4116,6 +4132,7 @@ static int finish_group_run(ksim_engine* const* engines, int world, int max_ev, 
   for (int k = 0; k < world; ++k) {  // one run: the same diagnostics on every engine of the group
     if (k > 0) engines[k]->stats = s;
     engines[k]->rep_ready = report;
+    engines[k]->ran = true;  // (a descheduling plan may follow: ksim_shard_group_deschedule)
   }
   return KSIM_OK;
 }
@@ -4332,6 +4349,8 @@ int ksim_shard_group_run(ksim_engine* const* engines, int world) {
   for (int k = 0; k < world; ++k) {
     engines[k]->rep_ready = false;
     engines[k]->stats = RunStats{};
+    engines[k]->ran = false;
+    engines[k]->ds.invalidate();
   }
   e0->shard.group.rmerge_n = -1;
   const RunEnv env = read_env();
@@ -4574,15 +4593,74 @@ int ksim_engine_get_nodes(ksim_engine* e, int replica, ksim_node* out) {
 
 }  // extern "C"
 
-// The descheduling plan of every replica from the last run's results and final node records (ksim_desched.hpp),
-// for every policy: mark, evaluate, the budgets on the host from the bound-pod counts (ksim_desched_host.hpp),
-// select.  The policy supplies the tag of its plan, the bytes per node of its select kernel's tables, its arguments
-// `a` with its own fields set, `ensure(tot, a)` for its per-event and victim buffers of tot elements and their
-// pointers in a, its eval kernel with what that takes after a, and its select kernel.
-template <class Args, class Ensure, class... Extra>
-static int desched_plan(ksim_engine* e, double ratio, DsPlan tag, int node_bytes, Args a, Ensure ensure,
-                        void (*eval)(Args, Extra...), void (*select)(Args), Extra... extra) {
-  if (e->shard.on()) return KSIM_ENOTSUP;
+// What a descheduling policy kind gives the plan driver below: the tag of its plan, the bytes per node of its select
+// kernel's tables, its victim record and where the plan (DeschedState) and a group's merge (ShardState::Group) keep
+// those, its kernel arguments with its own fields set, its per-event and victim buffers of tot elements with their
+// pointers in the arguments, the launch of its eval kernel, and its select kernel.
+struct FragPolicy {
+  using Args = ksim_ds::DsArgs;
+  using V = ksim_victim;
+  static constexpr DsPlan tag = kDsFrag;
+  static constexpr int node_bytes = ksim_ds::kSelNodeBytes;
+  static constexpr DevBuf<V> DeschedState::*vict = &DeschedState::vict;
+  static constexpr DevBuf<V> ShardState::Group::*merged = &ShardState::Group::d_vmerge;
+  static constexpr void (*select)(Args) = ksim_ds::k_desched_select;
+  int policy;
+  Args args() const {
+    Args a = {};
+    a.policy = policy;
+    return a;
+  }
+  int ensure(DeschedState& ds, size_t tot, Args& a) const {
+    int rc = ds.eval.ensure(tot);
+    if (!rc) rc = ds.plist.ensure(tot);
+    if (!rc) rc = ds.vict.ensure(tot);
+    a.eval = ds.eval.p, a.plist = ds.plist.p, a.vict = ds.vict.p;
+    return rc;
+  }
+  void eval(ksim_engine* e, dim3 grid, const Args& a) const {
+    hipLaunchKernelGGL(ksim_ds::k_desched_eval, grid, dim3(ksim_ds::kEvalBlock), 0, e->stream, a, (const TypDev*)e->d_tp.p);
+  }
+};
+struct CosPolicy {
+  using Args = ksim_ds::CosArgs;
+  using V = ksim_cos_victim;
+  static constexpr DsPlan tag = kDsCos;
+  static constexpr int node_bytes = ksim_ds::kCosNodeBytes;
+  static constexpr DevBuf<V> DeschedState::*vict = &DeschedState::cvict;
+  static constexpr DevBuf<V> ShardState::Group::*merged = &ShardState::Group::d_cmerge;
+  static constexpr void (*select)(Args) = ksim_ds::k_cos_select;
+  long long cpu_bar, gpu_bar;
+  Args args() const {
+    Args a = {};
+    a.cpu_bar = cpu_bar;
+    a.gpu_bar = gpu_bar;
+    return a;
+  }
+  int ensure(DeschedState& ds, size_t tot, Args& a) const {
+    int rc = ds.cos.ensure(tot);
+    if (!rc) rc = ds.cvict.ensure(tot);
+    a.rec = ds.cos.p, a.vict = ds.cvict.p;
+    return rc;
+  }
+  void eval(ksim_engine* e, dim3 grid, const Args& a) const {
+    hipLaunchKernelGGL(ksim_ds::k_cos_eval, grid, dim3(ksim_ds::kEvalBlock), 0, e->stream, a);
+  }
+};
+
+// The descheduling plan of every replica from the last run's results and final node records (ksim_desched.hpp), for
+// every policy, in three steps on the engine's stream, so that the shards of a group can take each step together
+// (group_plan) and an engine by itself takes them in a row (desched_plan):
+//   plan_eval    the buffers, mark, evaluate, and the bound-pod counts on their way to the host (no wait);
+//   plan_select  once the stream has been waited for: the budgets on the host (ksim_desched_host.hpp), select, and
+//                the victim counts on their way to the host;
+//   plan_finish  the wait, the plan's time and its tag.
+// A node-sharded engine makes its part: mark and eval under the ownership rule (eval_bound_node), so the bound pods
+// are those on its own nodes, and select capped at budget(ratio, creation events of its stream) -- the same number on
+// every shard and, bound <= creations, never below the cluster's budget, which no shard knows: its list then holds
+// every entry the merge can take from it (DESIGN.md "Descheduling on shards").
+template <class P>
+static int plan_eval(ksim_engine* e, const P& pol, typename P::Args& a) {
   if (!e->ran) return KSIM_ESTATE;
   DeschedState& ds = e->ds;
   ds.invalidate();
@@ -4590,13 +4668,13 @@ static int desched_plan(ksim_engine* e, double ratio, DsPlan tag, int node_bytes
   const int R = e->R;
   const int max_ev = ksim_ds_host::event_offsets(e->n_events.data(), R, ds.eoff);
   const size_t tot = (size_t)ds.eoff[R];
-  int rc = ensure(tot, a);
+  int rc = pol.ensure(ds, tot, a);
   if (!rc) rc = ds.gone.ensure(tot);
   if (!rc) rc = ds.cnt.ensure((size_t)3 * R);
   if (!rc) rc = ds.d_eoff.upload(ds.eoff, e->stream);
-  const size_t tab = (size_t)e->N * node_bytes;
+  const size_t tab = (size_t)e->N * P::node_bytes;
   const bool in_lds = tab <= (size_t)ksim_ds::kSelLdsBytes;
-  if (!rc && !in_lds) rc = ds.tab.ensure(ksim_ds::tab_stride(e->N, node_bytes) * R);
+  if (!rc && !in_lds) rc = ds.tab.ensure(ksim_ds::tab_stride(e->N, P::node_bytes) * R);
   if (rc) return rc;
   if (ds.ev0.ensure() || ds.ev1.ensure()) return KSIM_EHIP;
   a.reps = e->d_reps.p;
@@ -4607,6 +4685,8 @@ static int desched_plan(ksim_engine* e, double ratio, DsPlan tag, int node_bytes
   a.n_vict = ds.cnt.p + 2 * R;
   a.tab = in_lds ? nullptr : ds.tab.p;
   a.N = e->N;
+  a.node_off = e->shard.on() ? e->shard.node_off : 0;
+  a.sharded = e->shard.on() ? 1 : 0;
   KSIM_HIP(hipEventRecord(ds.ev0, e->stream));
   if (tot) KSIM_HIP(hipMemsetAsync(ds.gone.p, 0, tot, e->stream));
   KSIM_HIP(hipMemsetAsync(ds.cnt.p, 0, sizeof(int32_t) * 3 * R, e->stream));
@@ -4614,20 +4694,34 @@ static int desched_plan(ksim_engine* e, double ratio, DsPlan tag, int node_bytes
     const dim3 grid((unsigned)((max_ev + ksim_ds::kEvalBlock - 1) / ksim_ds::kEvalBlock), (unsigned)R);
     hipLaunchKernelGGL(ksim_ds::k_desched_mark, grid, dim3(ksim_ds::kEvalBlock), 0, e->stream, (ksim_ds::PlanArgs)a);
     KSIM_HIP(hipGetLastError());
-    hipLaunchKernelGGL(eval, grid, dim3(ksim_ds::kEvalBlock), 0, e->stream, a, extra...);
+    pol.eval(e, grid, a);
     KSIM_HIP(hipGetLastError());
   }
-  std::vector<int32_t> bound((size_t)R, 0);
-  KSIM_HIP(hipMemcpyAsync(bound.data(), a.bound, sizeof(int32_t) * R, hipMemcpyDeviceToHost, e->stream));
-  KSIM_HIP(hipStreamSynchronize(e->stream));
+  ds.bound.assign((size_t)R, 0);
+  KSIM_HIP(hipMemcpyAsync(ds.bound.data(), a.bound, sizeof(int32_t) * R, hipMemcpyDeviceToHost, e->stream));
+  return KSIM_OK;
+}
+
+template <class P>
+static int plan_select(ksim_engine* e, double ratio, const typename P::Args& a) {
+  DeschedState& ds = e->ds;
+  KSIM_HIP(hipSetDevice(e->device));
+  const int R = e->R;
+  ds.ratio = ratio;
   ds.budget.assign((size_t)R, 0);
-  for (int r = 0; r < R; ++r) ds.budget[r] = ksim_ds_host::budget(ratio, bound[r]);
+  for (int r = 0; r < R; ++r) ds.budget[r] = ksim_ds_host::budget(ratio, e->shard.on() ? e->n_create[r] : ds.bound[r]);
   KSIM_HIP(hipMemcpyAsync(ds.cnt.p + R, ds.budget.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, e->stream));
-  hipLaunchKernelGGL(select, dim3((unsigned)R), dim3(ksim_ds::kSelBlock), in_lds ? tab : (size_t)0, e->stream, a);
+  const size_t tab = (size_t)e->N * P::node_bytes;
+  hipLaunchKernelGGL(P::select, dim3((unsigned)R), dim3(ksim_ds::kSelBlock), a.tab ? (size_t)0 : tab, e->stream, a);
   KSIM_HIP(hipGetLastError());
   ds.nv.assign((size_t)R, 0);
   KSIM_HIP(hipMemcpyAsync(ds.nv.data(), a.n_vict, sizeof(int32_t) * R, hipMemcpyDeviceToHost, e->stream));
   KSIM_HIP(hipEventRecord(ds.ev1, e->stream));
+  return KSIM_OK;
+}
+
+static int plan_finish(ksim_engine* e, DsPlan tag) {
+  DeschedState& ds = e->ds;
   KSIM_HIP(hipStreamSynchronize(e->stream));
   float ms = 0;
   KSIM_HIP(hipEventElapsedTime(&ms, ds.ev0, ds.ev1));
@@ -4636,23 +4730,146 @@ static int desched_plan(ksim_engine* e, double ratio, DsPlan tag, int node_bytes
   return KSIM_OK;
 }
 
-// A replica's victims of the plan kTag, which the engine must hold, from that policy's victim buffer.
-template <DsPlan kTag, class V>
-static int plan_victims(ksim_engine* e, DevBuf<V> DeschedState::*vict, int replica, V* out, int cap, int* n_out,
-                        int* budget_out) {
+template <class P>
+static int desched_plan(ksim_engine* e, const P& pol, double ratio) {
+  typename P::Args a = pol.args();
+  int rc = plan_eval(e, pol, a);
+  if (rc) return rc;
+  KSIM_HIP(hipStreamSynchronize(e->stream));
+  if ((rc = plan_select<P>(e, ratio, a))) return rc;
+  return plan_finish(e, P::tag);
+}
+
+// A replica's victims of the plan of P's kind, which the engine must hold.  `part`: the engine's own list with the
+// pods bound on its nodes (ksim_engine_get_victim_part: on a shard its part, else the plan itself); otherwise the
+// plan with its budget, which a shard does not have -- its list is not the cluster's plan and may run past the
+// cluster's budget (KSIM_ENOTSUP).
+template <class P>
+static int plan_victims(ksim_engine* e, int replica, typename P::V* out, int cap, int* n_out, int* budget_out,
+                        int64_t* bound_out, bool part) {
   if (!e || replica < 0 || replica >= e->R || cap < 0 || !n_out) return KSIM_EINVAL;
+  if (!part && e->shard.on()) return KSIM_ENOTSUP;
   const DeschedState& ds = e->ds;
-  if (ds.plan != kTag) return KSIM_ESTATE;
+  if (ds.plan != P::tag) return KSIM_ESTATE;
   const int n = ds.nv[replica];
   *n_out = n;
   if (budget_out) *budget_out = ds.budget[replica];
+  if (bound_out) *bound_out = ds.bound[replica];
   if (cap < n) return KSIM_ERANGE;
   if (n == 0) return KSIM_OK;
   if (!out) return KSIM_EINVAL;
   KSIM_HIP(hipSetDevice(e->device));
-  KSIM_HIP(hipMemcpyAsync(out, (ds.*vict).p + ds.eoff[replica], sizeof(V) * n, hipMemcpyDeviceToHost, e->stream));
+  KSIM_HIP(hipMemcpyAsync(out, (ds.*P::vict).p + ds.eoff[replica], sizeof(typename P::V) * n, hipMemcpyDeviceToHost,
+                          e->stream));
   KSIM_HIP(hipStreamSynchronize(e->stream));
   return KSIM_OK;
+}
+
+static int group_check(ksim_engine* const* engines, int world) {
+  if (!engines || world < 1 || world > 16) return KSIM_EINVAL;
+  for (int k = 0; k < world; ++k)
+    if (!group_member_ok(engines, world, k)) return KSIM_EINVAL;
+  return KSIM_OK;
+}
+
+// The plan of an in-process group: every shard's part, each step of the driver on all shards before the next (the
+// shards' kernels are independent and sit on their own streams), the bound counts summed on the host, the cluster's
+// budget, then the merge of the shards' lists into engine 0's merged list (k_victim_merge) on engine 0's stream.
+// Engine 0's plan time spans the parts and the merge; KSIM_GROUP_TIMES=1 prints the merge's share on stderr.
+template <class P>
+static int group_plan(ksim_engine* const* engines, int world, const P& pol, double ratio) {
+  using V = typename P::V;
+  ksim_engine* e0 = engines[0];
+  ShardState::Group& g = e0->shard.group;
+  g.dplan = kDsNone;
+  for (int k = 0; k < world; ++k)
+    if (!engines[k]->ran) return KSIM_ESTATE;
+  std::vector<typename P::Args> as((size_t)world, pol.args());
+  int rc;
+  for (int k = 0; k < world; ++k)
+    if ((rc = plan_eval(engines[k], pol, as[k]))) return rc;
+  for (int k = 0; k < world; ++k) KSIM_HIP(hipStreamSynchronize(engines[k]->stream));
+  for (int k = 0; k < world; ++k)
+    if ((rc = plan_select<P>(engines[k], ratio, as[k]))) return rc;
+  for (int k = 0; k < world; ++k)
+    if ((rc = plan_finish(engines[k], P::tag))) return rc;
+  ksim_ds::MergeArgs<V> ma = {};
+  int64_t bound = 0, total = 0;
+  for (int k = 0; k < world; ++k) {
+    const DeschedState& ds = engines[k]->ds;
+    const int n = (int)std::min<long long>(std::max(ds.nv[0], 0), ds.eoff[1]);  // inside the shard's victim buffer
+    ma.part[k] = (ds.*P::vict).p;
+    ma.n[k] = n;
+    bound += ds.bound[0];
+    total += n;
+  }
+  if (bound > (int64_t)std::numeric_limits<int32_t>::max()) return KSIM_ERANGE;
+  const int32_t budget = ksim_ds_host::budget(ratio, (int32_t)bound);
+  const int take = (int)std::min<int64_t>(total, budget);
+  DevBuf<V>& merged = g.*P::merged;
+  if ((rc = merged.ensure((size_t)std::max(take, 1)))) return rc;
+  if ((rc = g.d_nmerge.ensure(1))) return rc;
+  if ((rc = g.d_margs.ensure(sizeof ma))) return rc;
+  ma.world = world;
+  ma.budget = budget;
+  ma.out = merged.p;
+  ma.out_cap = take;
+  ma.n_out = g.d_nmerge.p;
+  KSIM_HIP(hipSetDevice(e0->device));
+  hipStream_t st = e0->stream;
+  const bool times = read_env().group_times;
+  if (times) {
+    if ((rc = e0->tev_fork.ensure())) return rc;
+    KSIM_HIP(hipEventRecord(e0->tev_fork, st));
+  }
+  const unsigned blocks = (unsigned)std::max<int64_t>(1, (total + ksim_ds::kMergeBlock - 1) / ksim_ds::kMergeBlock);
+  KSIM_HIP(hipMemcpyAsync(g.d_margs.p, &ma, sizeof ma, hipMemcpyHostToDevice, st));  // (ma lives past the wait below)
+  hipLaunchKernelGGL((ksim_ds::k_victim_merge<V>), dim3(blocks), dim3(ksim_ds::kMergeBlock), 0, st,
+                     (const ksim_ds::MergeArgs<V>*)g.d_margs.p);
+  KSIM_HIP(hipGetLastError());
+  int32_t n_merged = -1;
+  KSIM_HIP(hipMemcpyAsync(&n_merged, g.d_nmerge.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  KSIM_HIP(hipEventRecord(e0->ds.ev1, st));
+  KSIM_HIP(hipStreamSynchronize(st));
+  if (n_merged != take) return KSIM_ESTATE;
+  float ms = 0, mms = 0;
+  KSIM_HIP(hipEventElapsedTime(&ms, e0->ds.ev0, e0->ds.ev1));
+  e0->ds.last_ms = ms;
+  if (times && hipEventElapsedTime(&mms, e0->tev_fork, e0->ds.ev1) == hipSuccess)
+    std::fprintf(stderr, "ksim group deschedule times (ms): %d shards' parts %.3f; merge %.3f\n", world, ms - mms, mms);
+  g.dgen.resize((size_t)world);
+  for (int k = 0; k < world; ++k) g.dgen[k] = engines[k]->ds.gen;
+  g.dmerge_n = take;
+  g.dbudget = budget;
+  g.dplan = P::tag;
+  return KSIM_OK;
+}
+
+// The merged list of the group's last plan, which must be of P's kind and made from the plans the shards still hold.
+template <class P>
+static int group_victims(ksim_engine* const* engines, int world, typename P::V* out, int cap, int* n_out,
+                         int* budget_out) {
+  if (int rc = group_check(engines, world)) return rc;
+  if (cap < 0 || !n_out) return KSIM_EINVAL;
+  ksim_engine* e0 = engines[0];
+  const ShardState::Group& g = e0->shard.group;
+  if (g.dplan != P::tag || g.dgen.size() != (size_t)world) return KSIM_ESTATE;
+  for (int k = 0; k < world; ++k)
+    if (engines[k]->ds.plan != P::tag || engines[k]->ds.gen != g.dgen[k]) return KSIM_ESTATE;
+  const int n = g.dmerge_n;
+  *n_out = n;
+  if (budget_out) *budget_out = g.dbudget;
+  if (cap < n) return KSIM_ERANGE;
+  if (n == 0) return KSIM_OK;
+  if (!out) return KSIM_EINVAL;
+  KSIM_HIP(hipSetDevice(e0->device));
+  KSIM_HIP(hipMemcpyAsync(out, (g.*P::merged).p, sizeof(typename P::V) * n, hipMemcpyDeviceToHost, e0->stream));
+  KSIM_HIP(hipStreamSynchronize(e0->stream));
+  return KSIM_OK;
+}
+
+static bool frag_policy_ok(int policy) {
+  return policy == KSIM_DESCHED_FRAG_ONE_POD || policy == KSIM_DESCHED_FRAG_MULTI_POD;
 }
 
 extern "C" {
@@ -4660,52 +4877,74 @@ extern "C" {
 int ksim_engine_deschedule(ksim_engine* e, int policy, double ratio) {
   if (check_gfx950(e ? e->device : 0)) return KSIM_ENODEV;
   if (!e) return KSIM_EINVAL;
-  if (policy != KSIM_DESCHED_FRAG_ONE_POD && policy != KSIM_DESCHED_FRAG_MULTI_POD) return KSIM_EINVAL;
+  if (!frag_policy_ok(policy)) return KSIM_EINVAL;
   if (!(ratio >= 0.0)) return KSIM_EINVAL;  // negative or NaN
-  ksim_ds::DsArgs a = {};
-  a.policy = policy;
-  DeschedState& ds = e->ds;
-  const auto ensure = [&ds](size_t tot, ksim_ds::DsArgs& a) {
-    int rc = ds.eval.ensure(tot);
-    if (!rc) rc = ds.plist.ensure(tot);
-    if (!rc) rc = ds.vict.ensure(tot);
-    a.eval = ds.eval.p, a.plist = ds.plist.p, a.vict = ds.vict.p;
-    return rc;
-  };
-  return desched_plan(e, ratio, kDsFrag, ksim_ds::kSelNodeBytes, a, ensure, ksim_ds::k_desched_eval,
-                      ksim_ds::k_desched_select, (const TypDev*)e->d_tp.p);
+  return desched_plan(e, FragPolicy{policy}, ratio);
 }
 
 int ksim_engine_get_victims(ksim_engine* e, int replica, ksim_victim* out, int cap, int* n_out, int* budget_out) {
-  return plan_victims<kDsFrag>(e, &DeschedState::vict, replica, out, cap, n_out, budget_out);
+  return plan_victims<FragPolicy>(e, replica, out, cap, n_out, budget_out, nullptr, false);
+}
+
+int ksim_engine_get_victim_part(ksim_engine* e, ksim_victim* out, int cap, int* n_out, int64_t* bound_out) {
+  return plan_victims<FragPolicy>(e, 0, out, cap, n_out, nullptr, bound_out, true);
 }
 
 int ksim_engine_deschedule_cossim(ksim_engine* e, double ratio, int64_t cpu_bar_milli, int64_t gpu_bar_milli) {
   if (check_gfx950(e ? e->device : 0)) return KSIM_ENODEV;
   if (!e) return KSIM_EINVAL;
   if (!(ratio >= 0.0) || cpu_bar_milli < 0 || gpu_bar_milli < 0) return KSIM_EINVAL;
-  ksim_ds::CosArgs a = {};
-  a.cpu_bar = (long long)cpu_bar_milli;
-  a.gpu_bar = (long long)gpu_bar_milli;
-  DeschedState& ds = e->ds;
-  const auto ensure = [&ds](size_t tot, ksim_ds::CosArgs& a) {
-    int rc = ds.cos.ensure(tot);
-    if (!rc) rc = ds.cvict.ensure(tot);
-    a.rec = ds.cos.p, a.vict = ds.cvict.p;
-    return rc;
-  };
-  return desched_plan(e, ratio, kDsCos, ksim_ds::kCosNodeBytes, a, ensure, ksim_ds::k_cos_eval, ksim_ds::k_cos_select);
+  return desched_plan(e, CosPolicy{(long long)cpu_bar_milli, (long long)gpu_bar_milli}, ratio);
 }
 
 int ksim_engine_get_cos_victims(ksim_engine* e, int replica, ksim_cos_victim* out, int cap, int* n_out,
                                 int* budget_out) {
-  return plan_victims<kDsCos>(e, &DeschedState::cvict, replica, out, cap, n_out, budget_out);
+  return plan_victims<CosPolicy>(e, replica, out, cap, n_out, budget_out, nullptr, false);
+}
+
+int ksim_engine_get_cos_victim_part(ksim_engine* e, ksim_cos_victim* out, int cap, int* n_out, int64_t* bound_out) {
+  return plan_victims<CosPolicy>(e, 0, out, cap, n_out, nullptr, bound_out, true);
 }
 
 int ksim_engine_last_deschedule_ms(ksim_engine* e, double* ms) {
   if (!e || !ms) return KSIM_EINVAL;
   *ms = e->ds.last_ms;
   return KSIM_OK;
+}
+
+int ksim_desched_merge(const ksim_victim* const* parts, const int* n, const int64_t* bound, int world, double ratio,
+                       ksim_victim* out, int cap, int* n_out, int* budget_out) {
+  return ksim_ds_host::merge_victims(parts, n, bound, world, ratio, out, cap, n_out, budget_out);
+}
+
+int ksim_cos_merge(const ksim_cos_victim* const* parts, const int* n, const int64_t* bound, int world, double ratio,
+                   ksim_cos_victim* out, int cap, int* n_out, int* budget_out) {
+  return ksim_ds_host::merge_cos_victims(parts, n, bound, world, ratio, out, cap, n_out, budget_out);
+}
+
+int ksim_shard_group_deschedule(ksim_engine* const* engines, int world, int policy, double ratio) {
+  if (int rc = group_check(engines, world)) return rc;
+  if (!frag_policy_ok(policy) || !(ratio >= 0.0)) return KSIM_EINVAL;
+  if (check_gfx950(engines[0]->device)) return KSIM_ENODEV;
+  return group_plan(engines, world, FragPolicy{policy}, ratio);
+}
+
+int ksim_shard_group_deschedule_cossim(ksim_engine* const* engines, int world, double ratio, int64_t cpu_bar_milli,
+                                       int64_t gpu_bar_milli) {
+  if (int rc = group_check(engines, world)) return rc;
+  if (!(ratio >= 0.0) || cpu_bar_milli < 0 || gpu_bar_milli < 0) return KSIM_EINVAL;
+  if (check_gfx950(engines[0]->device)) return KSIM_ENODEV;
+  return group_plan(engines, world, CosPolicy{(long long)cpu_bar_milli, (long long)gpu_bar_milli}, ratio);
+}
+
+int ksim_shard_group_get_victims(ksim_engine* const* engines, int world, ksim_victim* out, int cap, int* n_out,
+                                 int* budget_out) {
+  return group_victims<FragPolicy>(engines, world, out, cap, n_out, budget_out);
+}
+
+int ksim_shard_group_get_cos_victims(ksim_engine* const* engines, int world, ksim_cos_victim* out, int cap, int* n_out,
+                                     int* budget_out) {
+  return group_victims<CosPolicy>(engines, world, out, cap, n_out, budget_out);
 }
 
 }  // extern "C"

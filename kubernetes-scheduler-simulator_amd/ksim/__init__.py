@@ -226,6 +226,17 @@ SIGNATURES = {
     "ksim_engine_last_deschedule_ms": (C.c_int, [_VP, _P(C.c_double)]),
     "ksim_engine_deschedule_cossim": (C.c_int, [_VP, C.c_double, C.c_int64, C.c_int64]),
     "ksim_engine_get_cos_victims": (C.c_int, [_VP, C.c_int, _P(CosVictim), C.c_int, _P(C.c_int), _P(C.c_int)]),
+    "ksim_engine_get_victim_part": (C.c_int, [_VP, _P(Victim), C.c_int, _P(C.c_int), _P(C.c_int64)]),
+    "ksim_engine_get_cos_victim_part": (C.c_int, [_VP, _P(CosVictim), C.c_int, _P(C.c_int), _P(C.c_int64)]),
+    "ksim_desched_merge": (C.c_int, [_P(_P(Victim)), _P(C.c_int), _P(C.c_int64), C.c_int, C.c_double, _P(Victim),
+                                     C.c_int, _P(C.c_int), _P(C.c_int)]),
+    "ksim_cos_merge": (C.c_int, [_P(_P(CosVictim)), _P(C.c_int), _P(C.c_int64), C.c_int, C.c_double, _P(CosVictim),
+                                 C.c_int, _P(C.c_int), _P(C.c_int)]),
+    "ksim_shard_group_deschedule": (C.c_int, [_P(_VP), C.c_int, C.c_int, C.c_double]),
+    "ksim_shard_group_deschedule_cossim": (C.c_int, [_P(_VP), C.c_int, C.c_double, C.c_int64, C.c_int64]),
+    "ksim_shard_group_get_victims": (C.c_int, [_P(_VP), C.c_int, _P(Victim), C.c_int, _P(C.c_int), _P(C.c_int)]),
+    "ksim_shard_group_get_cos_victims": (C.c_int, [_P(_VP), C.c_int, _P(CosVictim), C.c_int, _P(C.c_int),
+                                                   _P(C.c_int)]),
 }
 
 
@@ -809,6 +820,25 @@ class Engine:
               "get_cos_victims")
         return [out[i] for i in range(n.value)], budget.value
 
+    def _part(self, fn, rec, what):
+        n, bound = C.c_int(0), C.c_int64(0)
+        rc = fn(self.h, None, 0, C.byref(n), C.byref(bound))
+        if rc != KSIM_ERANGE:
+            check(rc, what)
+        out = (rec * max(1, n.value))()
+        check(fn(self.h, out, n.value, C.byref(n), C.byref(bound)), what)
+        return [out[i] for i in range(n.value)], bound.value
+
+    def victim_part(self):
+        """(this engine's own victims in eviction order, the pods bound on its nodes) after deschedule(): on a shard
+        its part of the cluster's plan, node = the global rank (ksim.desched_merge merges the parts); on an
+        unsharded engine the plan of replica 0 itself."""
+        return self._part(lib().ksim_engine_get_victim_part, Victim, "get_victim_part")
+
+    def cos_victim_part(self):
+        """victim_part() of a cosSim plan (deschedule_cossim(); merged by ksim.cos_merge)."""
+        return self._part(lib().ksim_engine_get_cos_victim_part, CosVictim, "get_cos_victim_part")
+
     def last_deschedule_ms(self):
         ms = C.c_double(0)
         check(lib().ksim_engine_last_deschedule_ms(self.h, C.byref(ms)), "last_deschedule_ms")
@@ -886,6 +916,84 @@ def shard_group_reports(engines, power=False):
     pw = (PowerReport * max(1, n))() if power else None
     check(lib().ksim_shard_group_get_reports(arr, len(engines), out, pw, n), "shard_group_get_reports")
     return Engine._power_dicts(pw, n) if power else Engine._report_dicts(out, n)
+
+
+def _merge(fn, rec, parts, bounds, ratio, what):
+    arrs = []
+    for p in parts:
+        if isinstance(p, (bytes, bytearray, memoryview)):
+            b = bytes(p)
+            if len(b) % C.sizeof(rec):
+                raise ValueError("%s: not a whole number of %d-byte records" % (what, C.sizeof(rec)))
+            k = len(b) // C.sizeof(rec)
+            p = (rec * max(1, k)).from_buffer_copy(b.ljust(C.sizeof(rec), b"\0"))
+            arrs.append((p, k))
+        else:
+            p = list(p)
+            arrs.append(((rec * max(1, len(p)))(*p), len(p)))
+    if not arrs or len(arrs) != len(bounds):
+        raise ValueError("%s: one list and one bound count per shard" % what)
+    world = len(arrs)
+    ptrs = (_P(rec) * world)(*[C.cast(a, _P(rec)) for a, _ in arrs])
+    ns = (C.c_int * world)(*[k for _, k in arrs])
+    bs = (C.c_int64 * world)(*[int(b) for b in bounds])
+    total = sum(k for _, k in arrs)
+    out = (rec * max(1, total))()
+    n, budget = C.c_int(0), C.c_int(0)
+    check(fn(ptrs, ns, bs, world, float(ratio), out, total, C.byref(n), C.byref(budget)), what)
+    return [out[i] for i in range(n.value)], budget.value
+
+
+def desched_merge(parts, bounds, ratio):
+    """(victims, budget) of a node-sharded cluster from its shards' parts (ksim_desched_merge, on the host: no device
+    needed): parts holds one entry per shard in any order, the victim list of Engine.victim_part() or the bytes() of
+    its records, bounds the shards' bound-pod counts.  The parts are merged by (frag_before descending, node rank
+    ascending) and cut at ceil(ratio * sum(bounds)): the plan of the unsharded cluster, node = the global rank."""
+    return _merge(lib().ksim_desched_merge, Victim, parts, bounds, ratio, "desched_merge")
+
+
+def cos_merge(parts, bounds, ratio):
+    """desched_merge for cosSim parts (Engine.cos_victim_part(); ksim_cos_merge): merged by (gpu_left_milli
+    descending, node rank ascending)."""
+    return _merge(lib().ksim_cos_merge, CosVictim, parts, bounds, ratio, "cos_merge")
+
+
+def shard_group_deschedule(engines, policy, ratio):
+    """Plan on an in-process shard group after its run (ksim_shard_group_deschedule): every shard's part and the
+    merge on the device; returns engine 0's plan time in ms, which spans both."""
+    arr = (_VP * len(engines))(*[e.h for e in engines])
+    pol = DESCHED_POLICY[policy] if isinstance(policy, str) else int(policy)
+    check(lib().ksim_shard_group_deschedule(arr, len(engines), pol, float(ratio)), "shard_group_deschedule")
+    return engines[0].last_deschedule_ms()
+
+
+def shard_group_deschedule_cossim(engines, ratio, cpu_bar=COS_CPU_BAR_MILLI, gpu_bar=COS_GPU_BAR_MILLI):
+    """shard_group_deschedule by the cosSim policy (ksim_shard_group_deschedule_cossim)."""
+    arr = (_VP * len(engines))(*[e.h for e in engines])
+    check(lib().ksim_shard_group_deschedule_cossim(arr, len(engines), float(ratio), int(cpu_bar), int(gpu_bar)),
+          "shard_group_deschedule_cossim")
+    return engines[0].last_deschedule_ms()
+
+
+def _group_victims(fn, rec, engines, what):
+    arr = (_VP * len(engines))(*[e.h for e in engines])
+    n, budget = C.c_int(0), C.c_int(0)
+    rc = fn(arr, len(engines), None, 0, C.byref(n), C.byref(budget))
+    if rc != KSIM_ERANGE:
+        check(rc, what)
+    out = (rec * max(1, n.value))()
+    check(fn(arr, len(engines), out, n.value, C.byref(n), C.byref(budget)), what)
+    return [out[i] for i in range(n.value)], budget.value
+
+
+def shard_group_victims(engines):
+    """(the merged victims of the group's last frag plan, the cluster's budget); node = the global rank."""
+    return _group_victims(lib().ksim_shard_group_get_victims, Victim, engines, "shard_group_get_victims")
+
+
+def shard_group_cos_victims(engines):
+    """(the merged victims of the group's last cosSim plan, the cluster's budget); node = the global rank."""
+    return _group_victims(lib().ksim_shard_group_get_cos_victims, CosVictim, engines, "shard_group_get_cos_victims")
 
 
 def make_pod(cpu, milli=0, num=0, mem=0, type_mask=KSIM_TYPE_ANY, cpu_nz=None):

@@ -76,3 +76,24 @@ def run(engine, policy, ratio, cpu_bar=COS_CPU_BAR_MILLI, gpu_bar=COS_GPU_BAR_MI
             o["stage_nodes"] = dict(InitSchedule=init_nodes[r], PostEviction=evicted_nodes[r],
                                     PostDeschedule=engine.nodes(r))
     return out
+
+
+def run_group(group, policy, ratio, cpu_bar=COS_CPU_BAR_MILLI, gpu_bar=COS_GPU_BAR_MILLI):
+    """run() without stages for a ksim.shard.ShardGroup: plan on the group's last run() (every shard's part, merged
+    on the device), extend the stream with the cluster's victims, load it on every shard and run the group again.
+    Returns the same dict as run() gives per replica (victims: node = the input index)."""
+    if policy == COS_SIM:
+        group.deschedule_cossim(ratio, cpu_bar, gpu_bar)
+        victims, budget = group.cos_victims()
+    else:
+        group.deschedule(policy, ratio)
+        victims, budget = group.victims()
+    e0 = group.engines[0]
+    n = e0.n_events[0]
+    src = (Pod * max(1, n)).from_buffer_copy(e0.events[0].tobytes()) if n else (Pod * 1)()
+    ext = extend_events(src, n, victims)
+    n_ext = n + 2 * len(victims)
+    group.load_events(ext, n_ext)
+    group.run()
+    return dict(victims=victims, budget=budget, events=ext, n=n_ext, n_original=n,
+                post_eviction=n + len(victims) - 1, post_deschedule=n_ext - 1)

@@ -46,6 +46,26 @@ def merge_results(per_shard, parts):
     return out
 
 
+def victims_by_index(victims, parts):
+    """Copies of merged victim records with `node` mapped from the global rank to the input index, as
+    merge_results maps a result's node."""
+    index_of_rank = {off + j: i for off, _, idx in parts for j, i in enumerate(idx)}
+    out = []
+    for v in victims:
+        w = type(v).from_buffer_copy(bytes(v))
+        w.node = index_of_rank[v.node]
+        out.append(w)
+    return out
+
+
+def merge_victims(parts_per_shard, bounds, ratio, parts, cos=False):
+    """(victims, budget) of the cluster from one Engine.victim_part() list (cos: cos_victim_part(); or the bytes of
+    its records) and one bound-pod count per shard: ksim.desched_merge / ksim.cos_merge on the host, then node =
+    the input index.  parts: partition()'s."""
+    victims, budget = (ksim.cos_merge if cos else ksim.desched_merge)(parts_per_shard, bounds, ratio)
+    return victims_by_index(victims, parts), budget
+
+
 def merge_reports(parts_per_shard):
     """(reports, power_reports) of the cluster from one Engine.report_parts() array (or its bytes) per shard:
     ksim.report_merge, the exact integer sum rounded once."""
@@ -96,6 +116,33 @@ class ShardGroup:
         """Each shard's exact per-event records (Engine.report_parts), in shard order."""
         return [e.report_parts(0) for e in self.engines]
 
+    # descheduling (ksim_engine.h "Descheduling on a node-sharded cluster"); ksim.desched.run_group reschedules
+    def deschedule(self, policy, ratio):
+        """Plan "fragOnePod" / "fragMultiPod" on the last run(): every shard's part, merged on the device
+        (ksim_shard_group_deschedule).  Returns engine 0's plan time in ms, the merge included."""
+        return ksim.shard_group_deschedule(self.engines, policy, ratio)
+
+    def deschedule_cossim(self, ratio, cpu_bar=ksim.COS_CPU_BAR_MILLI, gpu_bar=ksim.COS_GPU_BAR_MILLI):
+        """Plan by the cosSim policy (ksim_shard_group_deschedule_cossim)."""
+        return ksim.shard_group_deschedule_cossim(self.engines, ratio, cpu_bar, gpu_bar)
+
+    def victims(self):
+        """(the cluster's victims in eviction order, budget) of the last frag plan: the device merge, node = the
+        input index as in results()."""
+        victims, budget = ksim.shard_group_victims(self.engines)
+        return victims_by_index(victims, self.parts), budget
+
+    def cos_victims(self):
+        """(the cluster's victims, budget) of the last cosSim plan, node = the input index."""
+        victims, budget = ksim.shard_group_cos_victims(self.engines)
+        return victims_by_index(victims, self.parts), budget
+
+    def victim_parts(self, cos=False):
+        """Each shard's own list and bound-pod count (Engine.victim_part; cos: cos_victim_part), in shard order:
+        ([lists], [bounds]), node = the global rank, as ksim.desched_merge / ksim.cos_merge take them."""
+        got = [e.cos_victim_part() if cos else e.victim_part() for e in self.engines]
+        return [g[0] for g in got], [g[1] for g in got]
+
     def close(self):
         for e in self.engines:
             e.close()
@@ -119,7 +166,7 @@ def host_gather(dist, group=None):
 
 
 def run_distributed(nodes, typical, events, n, dist, policy="FGD", seed=0, device=0, engine_cls=None,
-                    exchange="rccl", report=False, power_model=None):
+                    exchange="rccl", report=False, power_model=None, desched=None):
     """One shard per process (torchrun; backend nccl = RCCL for the launcher's own collectives):
     rank 0 makes the RCCL id of the shards' exchange, every rank builds its shard engine on
     `device`, replays the events, and the per-shard results are gathered and merged on every rank.
@@ -130,7 +177,11 @@ def run_distributed(nodes, typical, events, n, dist, policy="FGD", seed=0, devic
     report=True: every shard also reports its own nodes; the ranks gather the exact records (all_gather_object of
     their bytes) and each merges them on the host (merge_reports).  power_model: the [Power] report's energy model.
     Returns (merged results, device ms of this rank's run), with report=True (merged results, ms, reports): the
-    cluster's report per event, each with its power report under "power" when a power_model was given."""
+    cluster's report per event, each with its power report under "power" when a power_model was given.
+    desched=(policy, ratio) or ("cosSim", ratio, cpu_bar, gpu_bar): after its run each rank plans its part; the ranks
+    gather the parts' bytes and bound counts and each merges them on the host (merge_victims).  The return value gains
+    (victims, budget) as its last element.  Rescheduling is a second run_distributed on the extended stream
+    (ksim.desched.extend_events), left to the caller."""
     engine_cls = engine_cls or ksim.Engine
     rank, world = dist.get_rank(), dist.get_world_size()
     parts = partition(nodes, world)
@@ -162,19 +213,34 @@ def run_distributed(nodes, typical, events, n, dist, policy="FGD", seed=0, devic
     ms = e.run()
     mine = e.results(0)
     my_parts = bytes(e.report_parts(0)) if report else None
+    my_plan = None
+    if desched is not None:
+        cos = desched[0] == "cosSim"
+        if cos:
+            e.deschedule_cossim(*desched[1:])
+            mine_v, bound = e.cos_victim_part()
+        else:
+            e.deschedule(*desched)
+            mine_v, bound = e.victim_part()
+        my_plan = (b"".join(bytes(v) for v in mine_v), bound)
     e.close()
     gathered = [None] * world
     dist.all_gather_object(gathered, mine)
     merged = merge_results(gathered, parts)
+    plan = ()
+    if desched is not None:
+        plans = [None] * world
+        dist.all_gather_object(plans, my_plan)
+        plan = (merge_victims([p[0] for p in plans], [p[1] for p in plans], desched[1], parts, cos=cos),)
     if not report:
-        return merged, ms
+        return (merged, ms) + plan
     all_parts = [None] * world
     dist.all_gather_object(all_parts, my_parts)
     reports, power = merge_reports(all_parts)
     if power_model is not None:
         for r, p in zip(reports, power):
             r["power"] = p
-    return merged, ms, reports
+    return (merged, ms, reports) + plan
 
 
 def shard_comm_id_for(engine_cls):
