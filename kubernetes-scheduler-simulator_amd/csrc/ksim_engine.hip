@@ -4240,7 +4240,7 @@ static int run_replay_group(ksim_engine* const* engines, int world, const RunEnv
   int N = 1;  // slices cover the largest shard
   for (int k = 0; k < world; ++k) N = std::max(N, engines[k]->N);
   const int pol = e0->reps[0].policy;
-  const ShardSlices sl = replay_group_slices(N, world, e0->cus, pol);
+  const ShardSlices sl = replay_group_slices(N, world, e0->cus, pol, env.group_k);
   if (!sl.ok) return KSIM_OK;
   const int K = sl.K, S = sl.S, Kt = world * K;
   const bool general = e0->report;  // the report stores (snap / prev) are the general instantiation's

@@ -216,6 +216,7 @@ struct RunEnv {
   bool force_report_overlap = false;                                                       // KSIM_TEST report_overlap
   long pf_memo_ver0 = 0;                                                                   // KSIM_TEST
   bool pf_guess = true;
+  int group_k = 0;  // KSIM_TEST group_k=<K>: the in-process k_replay shard group at K slices per shard (replay_group_slices)
   int hdelay = 0;  // KSIM_TEST hdelay=<mask>: the memoised kernels' hand-over stress delays (ksim_memo.hpp hdelay; the
                    // bits are per kernel); a nonzero mask selects the instantiations that carry them
   bool timers() const { return profile == 1; }
@@ -243,6 +244,7 @@ static RunEnv read_env() {
   v.force_report_overlap = test_knob("report_overlap", 0) != 0;
   v.pf_memo_ver0 = test_knob("pf_memo_ver0", 0);
   v.pf_guess = test_knob("pf_guess", 1) != 0;
+  v.group_k = (int)std::max(0l, std::min(test_knob("group_k", 0), 256l));
   v.hdelay = (int)(test_knob("hdelay", 0) & 0xff);
   return v;
 }

@@ -782,10 +782,12 @@ inline ReplayNarrow replay_narrow(int K, int cap, int Rg, int N, int wgs_req, co
 
 // Slices of the in-process k_replay shard group (lean cheap policies) over shards of at most nmax nodes: about 384
 // nodes each (choose_wgs), at most 256 columns over the world, widened until the layout fits in LDS; not ok when the
-// layout does not fit or the exchange would have a single column.
-inline ShardSlices replay_group_slices(int nmax, int world, int cus, int pol) {
-  int K = std::max(1, std::min(256 / world, (nmax + 383) / 384));
+// layout does not fit or the exchange would have a single column.  k_req > 0 (KSIM_TEST group_k: the tests' way to a
+// wide exchange on a small cluster): that many slices per shard instead of the 384-node rule, under the same clamps.
+inline ShardSlices replay_group_slices(int nmax, int world, int cus, int pol, int k_req = 0) {
+  int K = std::max(1, std::min(256 / world, k_req > 0 ? k_req : (nmax + 383) / 384));
   K = std::min(K, std::max(1, cus / world));
+  K = std::min(K, std::max(1, nmax));  // (the 384-node rule never asks for more slices than nodes; a k_req may)
   int S = (nmax + K - 1) / K;
   while (replay::replay_lds(S, pol, false) > kLdsMax && (K + 1) * world <= std::min(256, cus)) {
     ++K;

@@ -947,6 +947,30 @@ void check_shard_slices() {
           ++n;
         }
     }
+  // replay_group_slices with a requested width (KSIM_TEST group_k), written out: the request replaces the 384-node
+  // rule only -- the clamps (256 / world, cus / world, nmax), the LDS widening and `ok` stay
+  const int BF = (int)POL_BESTFIT, CL = (int)POL_CLUSTERING;
+  const struct { int nmax, world, cus, pol, k_req, K, S; bool ok; } want[] = {
+      {300, 2, 256, BF, 0, 1, 300, true},       // no request: one slice per shard, two columns
+      {300, 2, 256, BF, 33, 33, 10, true},      // 66 columns
+      {200, 3, 256, CL, 43, 43, 5, true},       // 129
+      {120, 5, 256, BF, 51, 51, 3, true},       // 255
+      {300, 2, 256, BF, 128, 128, 3, true},     // 256
+      {300, 2, 304, BF, 200, 128, 3, true},     // above 256 / world
+      {200, 3, 304, BF, 1000, 85, 3, true},     // above 256 / world, which is not a power of two
+      {300, 2, 64, BF, 100, 32, 10, true},      // above cus / world
+      {40, 2, 256, CL, 100, 40, 1, true},       // above nmax: one node per slice
+      {250, 1, 256, BF, 250, 250, 1, true},     // a world of one, wide
+      {250, 1, 256, BF, 1, 1, 250, false},      // a single column: not ok, as without a request
+      {50, 16, 256, BF, 64, 16, 4, true},       // sixteen shards
+      // the LDS widening still applies: 32 B per slot beside the 5248 B of shared state, so S + 1 <= 4956
+      {100000, 2, 256, BF, 2, 21, 4762, true},
+  };
+  for (const auto& c : want) {
+    const ShardSlices sl = replay_group_slices(c.nmax, c.world, c.cus, c.pol, c.k_req);
+    CHECK(sl.K == c.K && sl.S == c.S && sl.ok == c.ok);
+    CHECK(c.world * sl.K <= 256 && (long)sl.K * sl.S >= c.nmax);
+  }
   std::printf("shard_slices: compared=%ld\n", n);
 }
 
