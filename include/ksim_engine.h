@@ -350,7 +350,14 @@ int  ksim_engine_last_report_ms(ksim_engine* e, double* ms);
  * recv[4*rank]) over the caller's transport (gloo, MPI, sockets: shards on hosts or GPUs RCCL does
  * not connect) and return 0; a non-zero return or a gather without this shard's record at its rank
  * ends the run with KSIM_ESTATE.  One host round trip per pod step: a correctness and portability
- * path, not the fast one.  fn == NULL clears it. */
+ * path, not the fast one.  fn == NULL clears it.
+ * PWR and PWR+FGD shards (RCCL, the host exchange, an in-process group; an energy model on every shard,
+ * KSIM_ESTATE without one): NormalizeScore (pwr_score.go:104-141) takes the min / max raw score of the whole
+ * cluster, so a created pod takes TWO exchange rounds of the same 32-byte record -- round A {0, feasible count,
+ * error flag, raw min | max << 32}, round B {best packed key under the cluster's range, the same three}.  `fn`
+ * is called once per ROUND: twice for a created pod under a PWR policy, once for every other event; both
+ * rounds are checked alike.  An in-process group runs them on the per-pod kernels (k_step, k_step_pwr,
+ * k_shard_commit); the device-initiated exchange below stays FGD only. */
 #define KSIM_SHARD_ID_BYTES 128
 typedef int (*ksim_shard_exchange_fn)(const uint64_t* send /* 4 */, uint64_t* recv /* 4 * world */, void* user);
 int  ksim_shard_comm_id(uint8_t* out /* KSIM_SHARD_ID_BYTES */);

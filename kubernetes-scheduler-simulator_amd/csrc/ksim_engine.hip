@@ -554,10 +554,21 @@ __global__ __launch_bounds__(kBlock) void k_step(StepArgs a, const TypDev* __res
     __hip_atomic_fetch_max(&ac->hi, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   if (errb) __hip_atomic_fetch_or(&ac->err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (pwr) return;  // k_step_pwr finishes the cycle
+  if (pwr && a.mode != 2) return;  // k_step_pwr finishes the cycle
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every contribution performed before the ticket
   const unsigned t = __hip_atomic_fetch_add(&ac->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (t != (unsigned)(a.bpr - 1)) return;
+  if (pwr) {
+    // round A of a sharded PWR cycle: the shard's raw score range goes to the exchange, so that k_step_pwr
+    // normalizes with the cluster's.  The totals stay in the Accum for k_step_pwr (round B), which resets them.
+    a.send[0] = 0ull;
+    a.send[1] = (unsigned long long)__hip_atomic_load(&ac->nfeas, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    a.send[2] = (unsigned long long)__hip_atomic_load(&ac->err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    a.send[3] = (unsigned long long)(unsigned)__hip_atomic_load(&ac->lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) |
+                ((unsigned long long)(unsigned)__hip_atomic_load(&ac->hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) << 32);
+    __hip_atomic_store(&ac->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
 
   const unsigned long long best = __hip_atomic_exchange(&ac->best, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const int nfeas = __hip_atomic_exchange(&ac->nfeas, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -583,6 +594,9 @@ __global__ __launch_bounds__(kBlock) void k_step(StepArgs a, const TypDev* __res
 // score (pwr_score.go:104-141) with the replica's min / max raw score, the weighted sum with FGD
 // (framework.go:686-704, generic_scheduler.go:511-519), the packed argmax key, and the last
 // workgroup of the replica finishes the cycle as k_step does.
+// kShard (a.mode == 2, node-sharded): the range is the cluster's, from the shards' round-A records in a.recv, and the
+// last workgroup sends the shard's record instead of finishing the cycle; the unsharded form is what it was.
+template <bool kShard>
 __global__ __launch_bounds__(kBlock) void k_step_pwr(StepArgs a) {
   const int r = a.rep_first + (int)blockIdx.x / a.bpr;
   const int b = (int)blockIdx.x % a.bpr;
@@ -595,8 +609,22 @@ __global__ __launch_bounds__(kBlock) void k_step_pwr(StepArgs a) {
   if (p.flags & kPodDelete) return;
   ResultDev* res_slot = a.res_override ? a.res_override : (rp.res + step);
   Accum* ac = a.acc + r;
-  const int lo = __hip_atomic_load(&ac->lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const int hi = __hip_atomic_load(&ac->hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  int lo, hi;
+  if (kShard) {
+    // node-sharded cluster: NormalizeScore's range is the cluster's, from the shards' round-A records
+    // (the shards with feasible nodes, as k_shard_commit counts them)
+    lo = 0x7fffffff, hi = -1;
+    for (int k = 0; k < a.world; ++k) {
+      const unsigned long long* r4 = a.recv + 4 * k;
+      if ((int)r4[1] > 0) {
+        lo = min(lo, (int)(unsigned)(r4[3] & 0xffffffffull));
+        hi = max(hi, (int)(unsigned)(r4[3] >> 32));
+      }
+    }
+  } else {
+    lo = __hip_atomic_load(&ac->lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    hi = __hip_atomic_load(&ac->hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
   __shared__ unsigned long long s_rkey[kBlock / 64];
   const int n0 = b * a.NB;
   const int nb = max(0, min(a.NB, a.N - n0));
@@ -626,6 +654,14 @@ __global__ __launch_bounds__(kBlock) void k_step_pwr(StepArgs a) {
   const int glo = __hip_atomic_exchange(&ac->lo, 0x7fffffff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const int ghi = __hip_atomic_exchange(&ac->hi, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __hip_atomic_store(&ac->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (kShard) {
+    // round B of a sharded PWR cycle: the shard's best key under the cluster's range (k_shard_commit finishes)
+    a.send[0] = best;
+    a.send[1] = (unsigned long long)nfeas;
+    a.send[2] = (unsigned long long)anyerr;
+    a.send[3] = (unsigned long long)(unsigned)glo | ((unsigned long long)(unsigned)ghi << 32);
+    return;
+  }
   const int* rank2idx = reinterpret_cast<const int*>(rp.tags + (size_t)a.N * kTagStride);
   finish_cycle(a, rp, p, step, res_slot, best, nfeas, anyerr, glo, ghi, best ? rank2idx[key_rank(best)] : -1);
 }
@@ -1158,7 +1194,7 @@ void k_replay(ksim_replay::ReplayArgs a,
               rp.prev[p_step] = s_last[x];
               s_last[x] = p_step;
             }
-            out.node = n_lo + x;
+            out.node = a.group ? (int)key_rank(W) : n_lo + x;
             out.gpu_mask = mask;
             hrec = make_int2(n_lo + x, mask + 1);
           }
@@ -1167,7 +1203,15 @@ void k_replay(ksim_replay::ReplayArgs a,
     }
     if (lane == 0) {
       if (hist) hist[p_step] = hrec;
-      if (writer) rp.res[p_step] = out;
+      if (writer) {
+        rp.res[p_step] = out;
+      } else if (a.group && w == 0) {  // a shard that does not own the winner names it, as in commit()
+        const uint32_t rk = key_rank(W);
+        if (rk - (uint32_t)rp.node_off >= (uint32_t)rp.n_local) {
+          out.node = (int)rk;
+          rp.res[p_step] = out;
+        }
+      }
     }
     return true;
   };
@@ -1874,6 +1918,7 @@ struct ShardState {  // a node-sharded cluster's shard (ksim_engine_set_shard): 
     DevBuf<unsigned long long> d_rgran;     // k_replay group: exchange granules
     DevBuf<ReplicaDev> d_rgreps;            // its shards' replicas, and their list
     DevBuf<int> d_rglist;
+    DevBuf<TypDev> d_rgtp;                  // and, for PWR+FGD, each shard's typical table (kMaxTypical entries apiece)
     DevBuf<RepAcc> d_rmerge;                // the merged report records (k_report_merge)
     int rmerge_n = -1;  // events they hold (-1: no group run with the report on since the events were loaded)
     // the merged descheduling plan (k_victim_merge; ksim_shard_group_deschedule): the list of the policy kind
@@ -3065,7 +3110,7 @@ int ksim_engine_schedule(ksim_engine* e, int replica, const ksim_pod* pod, int32
   if (is_pwr_policy(e->reps[replica].policy) && !e->pw_set[replica]) return KSIM_ESTATE;
   hipLaunchKernelGGL(k_step, dim3(e->bpr), dim3(kBlock), 0, e->stream, a, (const TypDev*)e->d_tp.p);
   if (is_pwr_policy(e->reps[replica].policy))
-    hipLaunchKernelGGL(k_step_pwr, dim3(e->bpr), dim3(kBlock), 0, e->stream, a);
+    hipLaunchKernelGGL(k_step_pwr<false>, dim3(e->bpr), dim3(kBlock), 0, e->stream, a);
   KSIM_HIP(hipGetLastError());
   ResultDev r;
   KSIM_HIP(hipMemcpyAsync(&r, e->d_res1.p, sizeof r, hipMemcpyDeviceToHost, e->stream));
@@ -3287,6 +3332,20 @@ static int shard_local(ksim_engine* e, hipStream_t st, const int* base, int step
   KSIM_HIP(hipGetLastError());
   return KSIM_OK;
 }
+// A PWR policy's second round: the shard's scores normalized with the cluster's raw range (gathered after
+// shard_local), its best key to the exchange again.
+static int shard_pwr(ksim_engine* e, hipStream_t st, const int* base, int step_off) {
+  StepArgs a = base_args(e);
+  a.base = base;
+  a.step_off = step_off;
+  a.mode = 2;
+  a.send = e->shard.d_send.p;
+  a.recv = e->shard.d_recv.p;
+  a.world = e->shard.world;
+  hipLaunchKernelGGL(k_step_pwr<true>, dim3(e->bpr), dim3(kBlock), 0, st, a);
+  KSIM_HIP(hipGetLastError());
+  return KSIM_OK;
+}
 static int shard_commit(ksim_engine* e, hipStream_t st, const int* base, int step_off) {
   StepArgs a = base_args(e);
   a.base = base;
@@ -3315,29 +3374,44 @@ static int shard_exchange(ksim_engine* e, hipStream_t st) {
 static int run_sharded(ksim_engine* e, int max_ev) {
   int rc;
   ShardState& sh = e->shard;
-  if (sh.exchanges_on_host()) {  // the record goes through the caller's transport, one step at a time
+  // a PWR policy takes two rounds per pod: the raw score range (k_step), then the keys under the cluster's range
+  // (k_step_pwr); see DESIGN.md "PWR on shards"
+  const bool pwr = any_pwr(e);
+  if (sh.exchanges_on_host()) {  // the record goes through the caller's transport, one round at a time
     const size_t rec = 4 * sizeof(unsigned long long);
-    for (int s = 0; s < max_ev; ++s) {
-      if ((rc = shard_local(e, e->stream, nullptr, s))) return rc;
+    auto round = [&]() -> int {
       KSIM_HIP(hipMemcpyAsync(sh.h_send.data(), sh.d_send.p, rec, hipMemcpyDeviceToHost, e->stream));
       KSIM_HIP(hipStreamSynchronize(e->stream));
       if (sh.xfn(sh.h_send.data(), sh.h_recv.data(), sh.xuser) != 0) return KSIM_ESTATE;
       // the caller's gather must hold this shard's own record at its rank
       if (std::memcmp(sh.h_recv.data() + 4 * (size_t)sh.rank, sh.h_send.data(), rec) != 0) return KSIM_ESTATE;
       KSIM_HIP(hipMemcpyAsync(sh.d_recv.p, sh.h_recv.data(), rec * (size_t)sh.world, hipMemcpyHostToDevice, e->stream));
+      return KSIM_OK;
+    };
+    for (int s = 0; s < max_ev; ++s) {
+      if ((rc = shard_local(e, e->stream, nullptr, s))) return rc;
+      if (pwr && e->h_ev_cls[0][s] >= 0) {  // (a delete event has no scores to normalize: one round, as ever)
+        if ((rc = round())) return rc;
+        if ((rc = shard_pwr(e, e->stream, nullptr, s))) return rc;
+      }
+      if ((rc = round())) return rc;
       if ((rc = shard_commit(e, e->stream, nullptr, s))) return rc;
     }
     return KSIM_OK;
   }
   if (sh.needs_group_run()) return KSIM_ESTATE;  // in-process group: ksim_shard_group_run
+  auto step = [&](const int* base, int i) {
+    int r = shard_local(e, e->stream, base, i);
+    if (!r && pwr && !(r = shard_exchange(e, e->stream))) r = shard_pwr(e, e->stream, base, i);
+    if (!r && !(r = shard_exchange(e, e->stream))) r = shard_commit(e, e->stream, base, i);
+    return r;
+  };
   hipGraph_t g = nullptr;
   GraphExec ge;
   const int K = std::min(e->K, std::max(max_ev, 1));
   if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
     bool ok = true;
-    for (int i = 0; i < K && ok; ++i)
-      ok = shard_local(e, e->stream, e->d_base.p, i) == KSIM_OK && shard_exchange(e, e->stream) == KSIM_OK &&
-           shard_commit(e, e->stream, e->d_base.p, i) == KSIM_OK;
+    for (int i = 0; i < K && ok; ++i) ok = step(e->d_base.p, i) == KSIM_OK;
     if (ok) hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, e->stream, e->d_base.p, K);
     const hipError_t ce = hipStreamEndCapture(e->stream, &g);
     if (ok && ce == hipSuccess && hipGraphInstantiate(&ge.h, g, nullptr, nullptr, 0) != hipSuccess) ge.h = nullptr;
@@ -3351,11 +3425,8 @@ static int run_sharded(ksim_engine* e, int max_ev) {
     }
     return KSIM_OK;
   }
-  for (int s = 0; s < max_ev; ++s) {
-    if ((rc = shard_local(e, e->stream, nullptr, s))) return rc;
-    if ((rc = shard_exchange(e, e->stream))) return rc;
-    if ((rc = shard_commit(e, e->stream, nullptr, s))) return rc;
-  }
+  for (int s = 0; s < max_ev; ++s)
+    if ((rc = step(nullptr, s))) return rc;
   return KSIM_OK;
 }
 
@@ -3371,7 +3442,7 @@ static int build_graph(ksim_engine* e) {
   for (int i = 0; i < e->K; ++i) {
     a.step_off = i;
     hipLaunchKernelGGL(k_step, dim3(e->bpr * e->R), dim3(kBlock), 0, e->stream, a, (const TypDev*)e->d_tp.p);
-    if (pwr) hipLaunchKernelGGL(k_step_pwr, dim3(e->bpr * e->R), dim3(kBlock), 0, e->stream, a);
+    if (pwr) hipLaunchKernelGGL(k_step_pwr<false>, dim3(e->bpr * e->R), dim3(kBlock), 0, e->stream, a);
   }
   hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, e->stream, e->d_base.p, e->K);
   KSIM_HIP(hipStreamEndCapture(e->stream, &g));
@@ -3856,9 +3927,10 @@ int ksim_engine_run(ksim_engine* e) {
                             (e->reps[r].gpusel != SEL_BEST && e->reps[r].gpusel != SEL_WORST && e->reps[r].gpusel != SEL_RANDOM)))
       return KSIM_ENOTSUP;
   if (e->shard.runs_peer()) rc = run_hmemo_peer(e, env, max_ev);
-  else if (e->shard.on()) rc = any_pwr(e) ? KSIM_ENOTSUP : run_sharded(e, max_ev);
+  else if (e->shard.on()) rc = run_sharded(e, max_ev);
   else rc = step_path ? run_graph(e, max_ev) : run_persistent(e, env, max_ev);
-  if (!rc && e->shard.on()) note_kernel(e->stats, e->shard.runs_peer() ? "k_hmemo_wide" : "k_step");
+  if (!rc && e->shard.on())
+    note_kernel(e->stats, e->shard.runs_peer() ? "k_hmemo_wide" : any_pwr(e) ? "k_step+k_step_pwr" : "k_step");
   if (!rc && step_path) note_kernel(e->stats, any_pwr(e) ? "k_step+k_step_pwr" : "k_step");
   if (rc) return rc;
   KSIM_HIP(hipEventRecord(e->ev_mid, e->stream));
@@ -4066,13 +4138,14 @@ static int reset_shard_state(ksim_engine* e, hipStream_t st, bool results) {
 }
 
 // The end of a node-sharded replay on e's stream: the closing event, the wait, the fail word of its one launch
-// (fail_word false: the per-pod k_step path has none) -- KSIM_ESTATE for a replay that gave up -- and the time from
-// ev0 to the closing event into e->stats.
+// (fail_word false: the per-pod k_step path has none) -- KSIM_ESTATE for a replay that gave up, KSIM_ERANGE for
+// a raw PWR score outside the key field -- and the time from ev0 to the closing event into e->stats.
 static int end_replay(ksim_engine* e, hipEvent_t closing, bool fail_word) {
   KSIM_HIP(hipEventRecord(closing, e->stream));
   KSIM_HIP(hipStreamSynchronize(e->stream));
   int fail = 0;
   if (fail_word) KSIM_HIP(hipMemcpy(&fail, e->d_fail.p, sizeof(int), hipMemcpyDeviceToHost));
+  if (fail & 2) return KSIM_ERANGE;  // a raw PWR score outside the 24-bit key field (as ksim_engine_run)
   if (fail) return KSIM_ESTATE;
   float ms = 0;
   KSIM_HIP(hipEventElapsedTime(&ms, e->ev0, closing));
@@ -4224,7 +4297,10 @@ static bool hmemo_group_eligible(ksim_engine* const* engines, int world, const R
 // with the cluster report on, the general instantiation (its report stores) where its layout fits.
 static bool replay_group_eligible(ksim_engine* const* engines, int world, const RunEnv& env) {
   const int pol = engines[0]->reps[0].policy;
-  if (pol < POL_BESTFIT || pol > POL_RANDOM || variant("shard_replay", 1) == 0) return false;
+  // the PWR policies too: plain PWR's one key round (the argmax of NormalizeScore is the argmax of the raw score) and
+  // PWR+FGD's round of A totals and guessed-range keys, with its miss round, span the shards' columns as a cheap
+  // policy's round does -- the cluster's raw range comes out of the same granules
+  if (((pol < POL_BESTFIT || pol > POL_RANDOM) && !is_pwr_policy(pol)) || variant("shard_replay", 1) == 0) return false;
   for (int k = 0; k < world; ++k) {
     const ksim_engine* e = engines[k];
     if (e->R != 1 || e->reps[0].policy != pol || e->run_mode == 1 || e->has_delete[0] || go_random(e, 0)) return false;
@@ -4268,10 +4344,18 @@ static int run_replay_group(ksim_engine* const* engines, int world, const RunEnv
   }
   ReplayArgs ra =
       replay_args(e0->shard.group.d_rgreps.p, e0->shard.group.d_rglist.p, N, K, S, e0->shard.group.d_rgran.p, nullptr, max_ev, e0->d_fail.p, skip, Kt);
+  ra.pf_guess = env.pf_guess ? 1 : 0;  // (PWR+FGD; its per-class memo stays off in a group: pm_c = 0)
   KSIM_HIP(hipMemsetAsync(e0->shard.group.d_rgran.p, 0, sizeof(unsigned long long) * 2 * (size_t)Kt * kGranW, st));
   KSIM_HIP(hipMemsetAsync(e0->d_fail.p, 0, sizeof(int), st));
   KSIM_HIP(hipEventRecord(e0->ev0, st));
-  const TypDev* tp = e0->d_tp.p;  // (the cheap policies read no typical table)
+  const TypDev* tp = e0->d_tp.p;  // (the cheap policies and PWR read no typical table)
+  if (pol == POL_PWR_FGD) {  // the kernel reads replica r's table at tp + r * kMaxTypical, r the shard's place in the list
+    if ((rc = e0->shard.group.d_rgtp.ensure((size_t)16 * kMaxTypical))) return rc;
+    for (int k = 0; k < world; ++k)
+      KSIM_HIP(hipMemcpyAsync(e0->shard.group.d_rgtp.p + (size_t)k * kMaxTypical, engines[k]->d_tp.p,
+                              sizeof(TypDev) * kMaxTypical, hipMemcpyDeviceToDevice, st));
+    tp = e0->shard.group.d_rgtp.p;
+  }
   if ((rc = launch_persistent(f, Kt, kRBlock, lds, st, e0->coop, ra, tp))) return rc;
   if ((rc = finish_group_run(engines, world, max_ev, K, "k_replay_group", false))) return rc;
   *done = true;
@@ -4345,6 +4429,11 @@ int ksim_shard_group_run(ksim_engine* const* engines, int world) {
     if (e->report != e0->report) return KSIM_EINVAL;            // and reports, or none does: the records are merged
     max_ev = std::max(max_ev, e->n_events[0]);
   }
+  for (int k = 0; k < world; ++k) {
+    // every shard takes the same rounds per pod; as ksim_engine_run, a PWR policy scores with the shard's power model
+    if (is_pwr_policy(engines[k]->reps[0].policy) != is_pwr_policy(e0->reps[0].policy)) return KSIM_EINVAL;
+    if (is_pwr_policy(engines[k]->reps[0].policy) && !engines[k]->pw_set[0]) return KSIM_ESTATE;
+  }
   KSIM_HIP(hipSetDevice(e0->device));
   for (int k = 0; k < world; ++k) {
     engines[k]->rep_ready = false;
@@ -4364,7 +4453,10 @@ int ksim_shard_group_run(ksim_engine* const* engines, int world) {
     const int rc = run_replay_group(engines, world, env, max_ev, &done);
     if (rc || done) return rc;
   }
-  for (int k = 0; k < world; ++k) engines[k]->stats.kernels = "k_step";  // (named first: a failed run names its path too)
+  // a PWR policy: two rounds per pod (the raw score range, then the keys under the cluster's range)
+  const bool pwr = any_pwr(e0);
+  const char* path = pwr ? "k_step+k_step_pwr" : "k_step";
+  for (int k = 0; k < world; ++k) engines[k]->stats.kernels = path;  // (named first: a failed run names its path too)
   if (int rc = e0->shard.group.d_ptrs.ensure(32)) return rc;
   std::vector<unsigned long long*> ptrs(32, nullptr);
   for (int k = 0; k < world; ++k) {
@@ -4379,16 +4471,25 @@ int ksim_shard_group_run(ksim_engine* const* engines, int world) {
     if ((rc = reset_shard_state(engines[k], st, false))) return rc;
   }
   KSIM_HIP(hipEventRecord(e0->ev0, st));
-  for (int s = 0; s < max_ev; ++s) {
-    for (int k = 0; k < world; ++k)
-      if ((rc = shard_local(engines[k], st, nullptr, s))) return rc;
+  auto gather = [&]() -> int {
     hipLaunchKernelGGL(k_shard_gather, dim3(1), dim3(1024), 0, st, (unsigned long long* const*)e0->shard.group.d_ptrs.p,
                        (unsigned long long* const*)(e0->shard.group.d_ptrs.p + 16), world);
     KSIM_HIP(hipGetLastError());
+    return KSIM_OK;
+  };
+  for (int s = 0; s < max_ev; ++s) {
+    for (int k = 0; k < world; ++k)
+      if ((rc = shard_local(engines[k], st, nullptr, s))) return rc;
+    if ((rc = gather())) return rc;
+    if (pwr) {
+      for (int k = 0; k < world; ++k)
+        if ((rc = shard_pwr(engines[k], st, nullptr, s))) return rc;
+      if ((rc = gather())) return rc;
+    }
     for (int k = 0; k < world; ++k)
       if ((rc = shard_commit(engines[k], st, nullptr, s))) return rc;
   }
-  return finish_group_run(engines, world, max_ev, 0, "k_step", false);
+  return finish_group_run(engines, world, max_ev, 0, path, false);
 }
 
 int ksim_engine_set_report(ksim_engine* e, int enable) {
@@ -4533,7 +4634,7 @@ int ksim_engine_time_steps(ksim_engine* e, int n_steps, double* mean_kernel_us) 
     a.step_off = i;
     KSIM_HIP(hipEventRecord(evs[2 * i], e->stream));
     hipLaunchKernelGGL(k_step, dim3(e->bpr * e->R), dim3(kBlock), 0, e->stream, a, (const TypDev*)e->d_tp.p);
-    if (any_pwr(e)) hipLaunchKernelGGL(k_step_pwr, dim3(e->bpr * e->R), dim3(kBlock), 0, e->stream, a);
+    if (any_pwr(e)) hipLaunchKernelGGL(k_step_pwr<false>, dim3(e->bpr * e->R), dim3(kBlock), 0, e->stream, a);
     KSIM_HIP(hipEventRecord(evs[2 * i + 1], e->stream));
   }
   KSIM_HIP(hipStreamSynchronize(e->stream));

@@ -76,7 +76,9 @@ class ShardGroup:
     """`world` shards of one cluster on one device, run in lockstep (ksim_shard_group_run).
     report=True: every shard reports its own nodes after the replay and the records are merged on the device
     (reports() / power_reports(); report_parts() gives each shard's exact records).  power_model: the energy
-    model of the [Power] report, set on every shard."""
+    model of the [Power] report, set on every shard; a PWR policy ("PWR", "PWR 500 FGD 500": Engine.set_policy's
+    strings) needs it and schedules by it -- NormalizeScore's raw range is the whole cluster's, through the group
+    launch's exchange on a create-only stream, through a second exchange round per pod otherwise."""
 
     def __init__(self, nodes, typical, world, policy="FGD", seed=0, device=0, report=False, power_model=None):
         arr, n = typical
@@ -176,6 +178,9 @@ def run_distributed(nodes, typical, events, n, dist, policy="FGD", seed=0, devic
     every peer's IPC-mapped exchange buffer (ksim_engine_set_shard_peers); `dist` only carries the handles.
     report=True: every shard also reports its own nodes; the ranks gather the exact records (all_gather_object of
     their bytes) and each merges them on the host (merge_reports).  power_model: the [Power] report's energy model.
+    A PWR policy ("PWR", "PWR <w> FGD <w>") needs the power_model and runs over exchange="rccl" and "host" (two
+    exchange rounds per created pod: the shards' raw score ranges, then their keys under the cluster's range; the
+    host gather is called once per round) -- not over "device", which stays FGD only (KSIM_ENOTSUP).
     Returns (merged results, device ms of this rank's run), with report=True (merged results, ms, reports): the
     cluster's report per event, each with its power report under "power" when a power_model was given.
     desched=(policy, ratio) or ("cosSim", ratio, cpu_bar, gpu_bar): after its run each rank plans its part; the ranks
