@@ -104,8 +104,10 @@ def test_fuzz_cluster_report(case, name, pol, sel):
     # the per-event cluster report (analysis.go:59-119) on every path: the oracle's exact sums
     want_res, _, want = O.run_events(case["onodes"], case["otypical"], case["oevents"], policy=pol, gpu_sel=sel,
                                      seed=5, threads=16, with_report=True)
+    create_only = not any(e.get("delete") for e in case["oevents"])
     for mode, label in PATHS:
-        eng = ksim.Engine(len(case["onodes"]), 1, run_mode=mode)
+        k1 = label == "replay-K1"
+        eng = ksim.Engine(len(case["onodes"]), 1, run_mode=mode, wgs_per_replica=1 if k1 else 0)
         try:
             eng.set_nodes(0, case["nodes"])
             eng.set_typical(0, case["typical"], case["typical_n"])
@@ -113,6 +115,8 @@ def test_fuzz_cluster_report(case, name, pol, sel):
             eng.set_report(True)
             eng.load_events(0, case["events"], case["n_events"])
             eng.run()
+            if k1 and create_only and name != "FGD":  # one workgroup, lean, a cheap policy: k_scan1<*, kReport = true, *>
+                assert eng.last_run_path() == "k_scan1"
             assert eng.results(0) == want_res, label
             got = eng.reports(0)
         finally:
