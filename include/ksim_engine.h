@@ -71,9 +71,14 @@ enum ksim_policy {
     KSIM_POLICY_GPUCLUSTERING = 4,
     KSIM_POLICY_RANDOM = 5,
     KSIM_POLICY_PWR = 6,            /* PWRScore (pkg/simulator/plugin/pwr_score.go), weight 1000 */
-    KSIM_POLICY_PWR_FGD = 7         /* PWRScore + FGDScore, weighted (ksim_engine_set_weights; default
+    KSIM_POLICY_PWR_FGD = 7,        /* PWRScore + FGDScore, weighted (ksim_engine_set_weights; default
                                        500 / 500 = "PWR 500 FGD 500", generate_run_scripts.py:40) */
+    KSIM_POLICY_WEIGHTED = 8        /* any weighted combination of the plugins 0..6 but Random
+                                       (ksim_engine_set_plugin_weights; ksim_engine_run only, kernel k_wsum) */
 };
+/* Plugins of a KSIM_POLICY_WEIGHTED weight vector: plugin ids are the policy numbers KSIM_POLICY_FGD ..
+ * KSIM_POLICY_PWR (0..6). */
+#define KSIM_NUM_PLUGINS 7
 
 /* Open-Gpu-Share gpuSelMethod (pkg/type/config.go:36-42; "FGDScore" selects the FGD selector) */
 enum ksim_gpusel {
@@ -237,6 +242,25 @@ int  ksim_engine_set_policy(ksim_engine* e, int replica, int policy, int gpusel,
  * KSIM_POLICY_PWR_FGD, the two plugin weights of the scheduler configuration. */
 int  ksim_engine_set_power_model(ksim_engine* e, int replica, const ksim_power_model* pm);
 int  ksim_engine_set_weights(ksim_engine* e, int replica, int32_t w_pwr, int32_t w_fgd);
+/* KSIM_POLICY_WEIGHTED: one integer weight per score plugin, as generate_config_and_run.py's -FGD 700 -BestFit 300
+ * (:74-75, 243-245): every plugin with a positive weight is enabled.  Per creation event every enabled plugin scores
+ * every feasible node, BestFit's and PWR's raw scores go through their NormalizeScore over the feasible nodes of the
+ * cluster, every score is range-checked to 0..100, multiplied by its weight and summed (framework.go:635-710,
+ * generic_scheduler.go:511-519); a Score error or a score outside 0..100 on any feasible node gives KSIM_ERROR for
+ * the event unless only one node is feasible.  ksim_result.score is the winner's total.
+ *   KSIM_EINVAL   null pointer, bad replica
+ *   KSIM_ESTATE   the replica's policy is not KSIM_POLICY_WEIGHTED
+ *   KSIM_ERANGE   a negative weight, no positive weight, or 100 * sum(w) >= 2^24 (the packed key's score field)
+ *   KSIM_ENOTSUP  a positive weight on KSIM_POLICY_RANDOM (its PreScore pick is not reproducible); or the replica's
+ *                 selector is KSIM_GPUSEL_FGD / _PWR / _DOTPROD and that plugin's weight is 0 (allocateGpuIdFunc holds
+ *                 only the enabled plugins' selectors)
+ * ksim_engine_set_policy accepts KSIM_POLICY_WEIGHTED with any selector; the selector is checked here and again at
+ * run.  ksim_engine_set_plugin_cfg applies to the DotProduct term; a positive PWR weight needs the energy model
+ * (ksim_engine_run: KSIM_ESTATE without one).  ksim_engine_run of a WEIGHTED replica returns KSIM_ESTATE until its
+ * weights are set, and KSIM_ENOTSUP on a node-sharded engine or a shard group, in run_mode 1, and for a cluster that
+ * does not fit one workgroup's LDS (DESIGN.md §3 "k_wsum" has the sizes).  The plugin-level calls
+ * (ksim_engine_filter_score, _schedule, _reserve) return KSIM_ENOTSUP on a WEIGHTED replica. */
+int  ksim_engine_set_plugin_weights(ksim_engine* e, int replica, const int32_t* w /* [KSIM_NUM_PLUGINS] */);
 /* Workgroups per replica for one replica (0: the engine's choice, the default; at most 64).  An FGD replica with
  * wgs > 1 in an auto-mode engine whose other FGD replicas take one workgroup each runs k_memo at that width (the
  * keys in HBM when they do not fit in LDS) concurrently with the others -- the paper sweep's longest replay
@@ -414,7 +438,9 @@ int  ksim_engine_last_run_wgs(ksim_engine* e, int* wgs_per_replica);
  * (k_random_go: every replica Random on Go's stream, ksim_engine_set_go_stream), KSIM_PATH_SCAN1
  * (k_scan1: every replica a cheap policy on one 256-thread workgroup, every node scanned per pod;
  * a mix of k_scan1 and k_replay groups reports KSIM_PATH_REPLAY).  (8 was KSIM_PATH_PMEMO, the archived
- * r03 k_pmemo trial; it is not reused.) */
+ * r03 k_pmemo trial; it is not reused.)  KSIM_PATH_WSUM (k_wsum: every replica a KSIM_POLICY_WEIGHTED
+ * combination; a mix of k_wsum and other groups reports KSIM_PATH_REPLAY, or KSIM_PATH_MIXED with a memoised one). */
+#define KSIM_PATH_WSUM    9
 #define KSIM_PATH_REPLAY  0
 #define KSIM_PATH_MEMO    1
 #define KSIM_PATH_MIXED   2

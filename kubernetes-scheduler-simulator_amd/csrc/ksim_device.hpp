@@ -198,7 +198,8 @@ struct __align__(64) Accum {
 };
 
 enum : int { POL_FGD = 0, POL_BESTFIT = 1, POL_DOTPROD = 2, POL_PACKING = 3, POL_CLUSTERING = 4, POL_RANDOM = 5,
-             POL_PWR = 6, POL_PWR_FGD = 7 };
+             POL_PWR = 6, POL_PWR_FGD = 7, POL_WEIGHTED = 8 };
+constexpr int kNumPlugins = 7;  // POL_WEIGHTED's weight vector: one weight per plugin id POL_FGD .. POL_PWR
 enum : int { SEL_BEST = 0, SEL_WORST = 1, SEL_RANDOM = 2, SEL_FGD = 3, SEL_PWR = 4, SEL_DOTPROD = 5 };
 KSIM_HD bool is_pwr_policy(int pol) { return pol == POL_PWR || pol == POL_PWR_FGD; }
 
@@ -653,6 +654,32 @@ KSIM_HD int pwr_score(const NodeV& n, const PodDev& p, int cap, int cm, const Po
 
 // PWRScorePlugin.NormalizeScore (pwr_score.go:104-141)
 KSIM_HD int pwr_normalize(int s, int lo, int hi) { return lo == hi ? 100 : (int)((long long)(s - lo) * 100 / (hi - lo)); }
+
+// One node's total under a weight vector (POL_WEIGHTED): what the framework does with the plugins' raw scores of a
+// feasible node once every plugin has scored every feasible node (framework.go:635-710, generic_scheduler.go:511-519).
+//   raw[p]   plugin p's Score (read only where w[p] > 0)
+//   bf_lo/hi BestFit's min / max raw score over the feasible nodes: NormalizeScore (plugin_utils.go:48-74) maps
+//            raw to (raw - lo) * 100 / (hi - lo), and every node to 0 when hi == lo
+//   pw_lo/hi PWR's: PWRScorePlugin.NormalizeScore (pwr_score.go:104-141), the same map but 100 when hi == lo
+//   the other plugins have no NormalizeScore; then every plugin's score must lie in 0..100 (framework.go:686-704:
+//   *err otherwise, which aborts the cycle), is multiplied by the plugin's weight, and the products are summed.
+// Integer arithmetic on int64 as Go's; the total fits an int while 100 * sum(w) < 2^24 (the packed key's field).
+KSIM_HD int wsum_total(const int (&raw)[kNumPlugins], int bf_lo, int bf_hi, int pw_lo, int pw_hi,
+                       const int (&w)[kNumPlugins], bool* err) {
+  long long tot = 0;
+  bool e = false;
+#pragma unroll
+  for (int p = 0; p < kNumPlugins; ++p) {
+    if (w[p] <= 0) continue;
+    long long s = raw[p];
+    if (p == POL_BESTFIT) s = bf_hi == bf_lo ? 0 : ((long long)raw[p] - bf_lo) * 100 / ((long long)bf_hi - bf_lo);
+    if (p == POL_PWR) s = pw_hi == pw_lo ? 100 : ((long long)raw[p] - pw_lo) * 100 / ((long long)pw_hi - pw_lo);
+    e = e || s < 0 || s > 100;
+    tot += (long long)w[p] * s;
+  }
+  *err = e;
+  return (int)tot;
+}
 
 // x / 125 correctly rounded for every integer-valued x with |x| < 2^31, without a division: the product
 // with RN(1/125), its exact remainder by an fma, one fma correction.  Checked against IEEE division for

@@ -737,6 +737,7 @@ struct GranV {
 // step loop, as k_memo's does.
 #include "ksim_random_go.hpp"
 #include "ksim_scan1.hpp"
+#include "ksim_wsum.hpp"
 #include "ksim_desched.hpp"
 
 template <int kPol, int kSub, bool kGeneral>
@@ -2018,6 +2019,11 @@ struct ksim_engine {
   DevBuf<uint8_t> d_cpum; // [R][N] CPU model id per node
   DevBuf<int2> d_pws;     // [R][N] PWR phase-A scratch
   std::vector<char> pw_set;  // set_power_model called
+  // KSIM_POLICY_WEIGHTED: per replica the kNumPlugins weights and the plugin mask (k_wsum's argument table, uploaded
+  // at launch), and whether ksim_engine_set_plugin_weights has set them since the policy was set
+  std::vector<std::array<int32_t, ksim_wsum::kWStride>> wsum_w;
+  std::vector<char> wsum_set;
+  DevBuf<int> d_wsum;     // [R][kWStride]
   DevEvent ev0, ev1, ev_mid;
   MappedFlags started;  // residency gate: host-mapped flags, one per FGD workgroup
   int gate_epoch = 0;
@@ -2104,6 +2110,11 @@ static const void* scan1_fn(int pol) {
     case POL_RANDOM: return (const void*)ksim_scan1::k_scan1<POL_RANDOM, R, G>;
     default: return nullptr;
   }
+}
+// k_wsum by what the launch carries: FGD's evaluation, PWR's energy model, deletes and report stores
+template <bool F, bool P>
+static const void* wsum_fn(bool general) {
+  return general ? (const void*)ksim_wsum::k_wsum<F, P, true> : (const void*)ksim_wsum::k_wsum<F, P, false>;
 }
 static const void* scan1_fn(int pol, bool report, bool reg) {
   return report ? (reg ? scan1_fn<true, true>(pol) : scan1_fn<true, false>(pol))
@@ -2781,7 +2792,8 @@ static int init_replicas(ksim_engine* e) {
   const size_t n = (size_t)e->N;
   const auto per_replica = [R](auto&... v) { (v.resize(R), ...); };  // empty buffers, zero counts
   per_replica(e->reps, e->h_nodes, e->h_rec, e->h_cls, e->h_tp, e->h_cls_n, e->h_ev_cls, e->go_state, e->d_ev, e->d_res,
-              e->d_snap, e->d_prev, e->d_rep, e->n_events, e->has_delete, e->n_create, e->wgs_hint, e->nt, e->total_gpus, e->pw_set);
+              e->d_snap, e->d_prev, e->d_rep, e->n_events, e->has_delete, e->n_create, e->wgs_hint, e->nt, e->total_gpus, e->pw_set,
+              e->wsum_w, e->wsum_set);
   for (int r = 0; r < R; ++r) {
     ReplicaDev& rp = e->reps[r];
     std::memset(&rp, 0, sizeof rp);
@@ -2956,11 +2968,13 @@ int ksim_engine_set_typical(ksim_engine* e, int replica, const ksim_typical* tp,
 int ksim_engine_set_policy(ksim_engine* e, int replica, int policy, int gpusel, uint64_t seed) {
   if (e) e->mplan_dirty = true;
   if (!e || replica < 0 || replica >= e->R) return KSIM_EINVAL;
-  if (policy < POL_FGD || policy > POL_PWR_FGD || gpusel < SEL_BEST || gpusel > SEL_DOTPROD) return KSIM_ENOTSUP;
+  if (policy < POL_FGD || policy > POL_WEIGHTED || gpusel < SEL_BEST || gpusel > SEL_DOTPROD) return KSIM_ENOTSUP;
   // allocateGpuIdFunc only holds the selectors of the enabled plugins (fgd_score.go:37, pwr_score.go:40,
-  // dot_product_score.go:37)
-  if (gpusel == SEL_PWR && !is_pwr_policy(policy)) return KSIM_ENOTSUP;
-  if (gpusel == SEL_DOTPROD && policy != POL_DOTPROD) return KSIM_ENOTSUP;
+  // dot_product_score.go:37).  POL_WEIGHTED: which plugins are enabled is known with the weights
+  // (ksim_engine_set_plugin_weights checks the selector, and ksim_engine_run again)
+  if (policy != POL_WEIGHTED && gpusel == SEL_PWR && !is_pwr_policy(policy)) return KSIM_ENOTSUP;
+  if (policy != POL_WEIGHTED && gpusel == SEL_DOTPROD && policy != POL_DOTPROD) return KSIM_ENOTSUP;
+  if (policy == POL_WEIGHTED && e->reps[replica].policy != POL_WEIGHTED) e->wsum_set[replica] = 0;
   if (policy == POL_PWR_FGD && e->reps[replica].policy != POL_PWR_FGD) {
     e->reps[replica].w_pwr = 500;  // "PWR 500 FGD 500" (generate_run_scripts.py:40) until set_weights
     e->reps[replica].w_fgd = 500;
@@ -3030,6 +3044,34 @@ int ksim_engine_set_weights(ksim_engine* e, int replica, int32_t w_pwr, int32_t 
   return KSIM_OK;
 }
 
+// The selector of a POL_WEIGHTED replica against its weights: allocateGpuIdFunc holds only the enabled plugins'
+// selectors (fgd_score.go:37, pwr_score.go:40, dot_product_score.go:37).
+static bool wsum_selector_ok(int gpusel, const int32_t* w) {
+  if (gpusel == SEL_FGD) return w[POL_FGD] > 0;
+  if (gpusel == SEL_PWR) return w[POL_PWR] > 0;
+  if (gpusel == SEL_DOTPROD) return w[POL_DOTPROD] > 0;
+  return true;
+}
+
+int ksim_engine_set_plugin_weights(ksim_engine* e, int replica, const int32_t* w) {
+  static_assert(KSIM_NUM_PLUGINS == kNumPlugins && KSIM_POLICY_WEIGHTED == POL_WEIGHTED, "ksim_engine.h");
+  if (!e || !w || replica < 0 || replica >= e->R) return KSIM_EINVAL;
+  if (e->reps[replica].policy != POL_WEIGHTED) return KSIM_ESTATE;
+  // framework weights are positive; the packed key holds the total, at most 100 * sum(w), in 24 bits
+  long long sum = 0;
+  for (int p = 0; p < kNumPlugins; ++p) {
+    if (w[p] < 0) return KSIM_ERANGE;
+    sum += w[p];
+  }
+  if (sum <= 0 || 100 * sum >= (1ll << 24)) return KSIM_ERANGE;
+  if (w[POL_RANDOM] > 0) return KSIM_ENOTSUP;  // RandomScore's PreScore pick is not reproducible
+  if (!wsum_selector_ok(e->reps[replica].gpusel, w)) return KSIM_ENOTSUP;
+  std::copy(w, w + kNumPlugins, e->wsum_w[replica].begin());
+  e->wsum_w[replica][kNumPlugins] = (int32_t)ksim_plan::wsum::plugin_mask(w);
+  e->wsum_set[replica] = 1;
+  return KSIM_OK;
+}
+
 int ksim_engine_set_power_model(ksim_engine* e, int replica, const ksim_power_model* pm) {
   static_assert(sizeof(ksim_power_model) == sizeof(PowerDev), "ksim_power_model layout");
   if (!e || !pm || replica < 0 || replica >= e->R) return KSIM_EINVAL;
@@ -3071,7 +3113,7 @@ int ksim_engine_filter_score(ksim_engine* e, int replica, const ksim_pod* pod, i
   if (rc) return rc;
   if (p.flags & kPodDelete) return KSIM_EINVAL;
   // one plugin's Score per call: a weighted combination has two (query PWR and FGD replicas)
-  if (e->reps[replica].policy == POL_PWR_FGD) return KSIM_ENOTSUP;
+  if (e->reps[replica].policy == POL_PWR_FGD || e->reps[replica].policy == POL_WEIGHTED) return KSIM_ENOTSUP;
   if (is_pwr_policy(e->reps[replica].policy) && !e->pw_set[replica]) return KSIM_ESTATE;
   KSIM_HIP(hipSetDevice(e->device));
   KSIM_HIP(hipMemcpyAsync(e->d_pod.p, &p, sizeof p, hipMemcpyHostToDevice, e->stream));
@@ -3099,6 +3141,7 @@ int ksim_engine_schedule(ksim_engine* e, int replica, const ksim_pod* pod, int32
   int rc = to_pod_dev(*pod, &p);
   if (rc) return rc;
   if (p.flags & kPodDelete) return KSIM_EINVAL;  // deletions go through ksim_engine_unreserve
+  if (e->reps[replica].policy == POL_WEIGHTED) return KSIM_ENOTSUP;  // the weighted combinations: ksim_engine_run only
   KSIM_HIP(hipSetDevice(e->device));
   KSIM_HIP(hipMemcpyAsync(e->d_pod.p, &p, sizeof p, hipMemcpyHostToDevice, e->stream));
   StepArgs a = base_args(e);
@@ -3124,6 +3167,7 @@ int ksim_engine_reserve(ksim_engine* e, int replica, const ksim_pod* pod, int no
   PodDev p;
   int rc = to_pod_dev(*pod, &p);
   if (rc) return rc;
+  if (e->reps[replica].policy == POL_WEIGHTED) return KSIM_ENOTSUP;  // the weighted combinations: ksim_engine_run only
   KSIM_HIP(hipSetDevice(e->device));
   hipLaunchKernelGGL(k_reserve, dim3(1), dim3(64), 0, e->stream, e->d_reps.p, (const TypDev*)e->d_tp.p, replica, p, node, step, e->d_scratch.p, +1, -1);
   KSIM_HIP(hipGetLastError());
@@ -3509,7 +3553,8 @@ static bool dead_skip(const ksim_engine* e, const RunEnv& env, const std::vector
 static RunPlanInput run_plan_input(const ksim_engine* e, const RunEnv& env) {
   RunPlanInput in;
   for (int r = 0; r < e->R; ++r)
-    in.reps.push_back({e->reps[r].policy, go_random(e, r), e->n_events[r], (bool)e->has_delete[r], e->reps[r].dpcfg});
+    in.reps.push_back({e->reps[r].policy, go_random(e, r), e->n_events[r], (bool)e->has_delete[r], e->reps[r].dpcfg,
+                       e->reps[r].policy == POL_WEIGHTED ? (unsigned)e->wsum_w[r][kNumPlugins] : 0u});
   in.N = e->N;
   in.cus = e->cus;
   in.wgs_req = e->wgs_req;
@@ -3619,6 +3664,32 @@ static int launch_scan1(ksim_engine* e, const RunEnv& env, const RunPlan& plan, 
   void* params[] = {(void*)&sa};
   KSIM_HIP(hipLaunchKernel(f, dim3(g.count), dim3(ksim_scan1::kBlock), params, g.lds, gs));
   note_launch(e, mix ? "k_scan1_mix" : "k_scan1", 1, &e->stats.scan1, g.count);
+  return KSIM_OK;
+}
+
+// k_wsum (the weighted combinations): one 1024-thread workgroup per replica, the instantiation by what the group's
+// plugin masks and the run need.  A cluster that does not fit one workgroup's LDS is refused.
+// Its argument table (every replica's weights and plugin mask), uploaded before anything of the run is enqueued.
+static int upload_wsum_weights(ksim_engine* e, const RunPlan& plan) {
+  if (std::none_of(plan.groups.begin(), plan.groups.end(), [](const PlanGroup& g) { return g.kernel == kRunWsum; }))
+    return KSIM_OK;
+  std::vector<int> h((size_t)e->R * ksim_wsum::kWStride, 0);
+  for (int r = 0; r < e->R; ++r) std::copy(e->wsum_w[r].begin(), e->wsum_w[r].end(), h.begin() + (size_t)r * ksim_wsum::kWStride);
+  if (const int rc = e->d_wsum.upload(h, e->stream)) return rc;
+  KSIM_HIP(hipStreamSynchronize(e->stream));  // h is a local
+  return KSIM_OK;
+}
+static int launch_wsum(ksim_engine* e, const RunPlan& plan, int gi, hipStream_t gs) {
+  const PlanGroup& g = plan.groups[gi];
+  if (!wsum::wsum_fits(e->N, g.wmask, plan.general)) return KSIM_ENOTSUP;
+  const bool fgd = (g.wmask >> POL_FGD) & 1u, pwr = (g.wmask >> POL_PWR) & 1u;
+  const void* f = fgd ? (pwr ? wsum_fn<true, true>(plan.general) : wsum_fn<true, false>(plan.general))
+                      : (pwr ? wsum_fn<false, true>(plan.general) : wsum_fn<false, false>(plan.general));
+  ksim_wsum::WsumArgs wa{e->d_reps.p, e->d_replist.p + g.first, e->d_wsum.p, e->N, g.wmask};
+  const TypDev* tp = e->d_tp.p;
+  const int rc = launch_persistent(f, g.count, ksim_wsum::kBlock, g.lds, gs, false, wa, tp);
+  if (rc) return rc;
+  note_launch(e, "k_wsum", 1, &e->stats.wsum, g.count);
   return KSIM_OK;
 }
 
@@ -3858,6 +3929,7 @@ static int launch_group_reports(ksim_engine* e, const RunPlan& plan, int ovl_gro
 static int run_persistent(ksim_engine* e, const RunEnv& env, int max_ev) {
   const RunPlan plan = make_run_plan(run_plan_input(e, env));
   int rc = upload_go_states(e, plan);
+  if (!rc) rc = upload_wsum_weights(e, plan);
   if (rc) return rc;
   e->stats.launches = (int)plan.groups.size();
   KSIM_HIP(hipMemcpyAsync(e->d_replist.p, plan.order.data(), sizeof(int) * plan.order.size(), hipMemcpyHostToDevice, e->stream));
@@ -3877,6 +3949,7 @@ static int run_persistent(ksim_engine* e, const RunEnv& env, int max_ev) {
       case kRunHmemo: rc = launch_hmemo_group(e, env, plan, gi, gs, max_ev); break;
       case kRunReplay: rc = launch_replay(e, env, plan, gi, gs, max_ev); break;
       case kRunNone: rc = KSIM_ENOTSUP; break;
+      case kRunWsum: rc = launch_wsum(e, plan, gi, gs); break;
     }
     if (rc) return rc;
     if (ovl) ovl_group = gi;
@@ -3912,6 +3985,12 @@ int ksim_engine_run(ksim_engine* e) {
   e->grp_rev_used = 0;
   e->tev_used = 0u;  // KSIM_GROUP_TIMES: only run_persistent's concurrent groups record side-stream ends
   e->stats = RunStats{};
+  for (int r = 0; r < e->R; ++r) {  // the weighted combinations: k_wsum on the persistent path of an unsharded engine
+    if (e->reps[r].policy != POL_WEIGHTED) continue;
+    if (!e->wsum_set[r]) return KSIM_ESTATE;
+    if (e->wsum_w[r][POL_PWR] > 0 && !e->pw_set[r]) return KSIM_ESTATE;
+    if (e->shard.on() || e->run_mode == 1 || !wsum_selector_ok(e->reps[r].gpusel, e->wsum_w[r].data())) return KSIM_ENOTSUP;
+  }
   int rc = prepare_memo(e, env, max_ev);
   if (rc) return rc;
   KSIM_HIP(hipEventRecord(e->ev0, e->stream));
@@ -4433,6 +4512,7 @@ int ksim_shard_group_run(ksim_engine* const* engines, int world) {
     // every shard takes the same rounds per pod; as ksim_engine_run, a PWR policy scores with the shard's power model
     if (is_pwr_policy(engines[k]->reps[0].policy) != is_pwr_policy(e0->reps[0].policy)) return KSIM_EINVAL;
     if (is_pwr_policy(engines[k]->reps[0].policy) && !engines[k]->pw_set[0]) return KSIM_ESTATE;
+    if (engines[k]->reps[0].policy == POL_WEIGHTED) return KSIM_ENOTSUP;  // k_wsum holds the whole cluster in one workgroup
   }
   KSIM_HIP(hipSetDevice(e0->device));
   for (int k = 0; k < world; ++k) {
@@ -4621,6 +4701,8 @@ int ksim_engine_last_run_path(ksim_engine* e, int* path) {
 
 int ksim_engine_time_steps(ksim_engine* e, int n_steps, double* mean_kernel_us) {
   if (!e || !mean_kernel_us || n_steps <= 0) return KSIM_EINVAL;
+  for (int r = 0; r < e->R; ++r)
+    if (e->reps[r].policy == POL_WEIGHTED) return KSIM_ENOTSUP;  // k_step has no weighted combination but PWR+FGD
   KSIM_HIP(hipSetDevice(e->device));
   std::vector<DevEvent> evs(2 * n_steps);
   for (DevEvent& x : evs)

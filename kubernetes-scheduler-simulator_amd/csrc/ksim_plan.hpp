@@ -196,6 +196,42 @@ __host__ __device__ inline size_t scan1_lds(int N, int pol, bool report, bool re
 }
 }  // namespace scan1
 
+// ---- k_wsum: limits and LDS layout (ksim_wsum.hpp takes them from here) ----
+namespace wsum {
+constexpr int kBlock = 1024;           // thread t owns the node slots t, t + kBlock, ...
+constexpr size_t kSharedBytes = 5328;  // sizeof(WsumShared): the struct stays beside the kernel, which asserts it
+constexpr int kMaxNodes = kMaxSlice + 1;  // the packed key's slot field (one workgroup holds the whole cluster)
+// the plugins of a weight vector as a mask (bit p: w[p] > 0)
+inline unsigned plugin_mask(const int32_t* w) {
+  unsigned m = 0u;
+  for (int p = 0; p < kNumPlugins; ++p) m |= w[p] > 0 ? 1u << p : 0u;
+  return m;
+}
+// Dynamic LDS after WsumShared (16-B aligned regions): NodeRec nodes[N] | int4 sc[N] (the step's raw scores of every
+// slot, kept between the scan and the decision) | u16 tags[N][16] (GpuClustering in the mask: the tag counts) |
+// double F0[N] (FGD in the mask: cached F of the current state, < 0 = stale) | i32 last[N] (general: the report's
+// previous event per node).
+struct WLayout {
+  size_t nodes, sc, tags, F0, last, total;
+};
+__host__ __device__ inline WLayout wsum_layout(int N, unsigned mask, bool general) {
+  const size_t n = (size_t)N;
+  WLayout L;
+  size_t o = kSharedBytes;
+  L.nodes = o; o += n * sizeof(NodeRec);
+  L.sc = o;    o += n * 16;
+  L.tags = o;  o += ((mask >> POL_CLUSTERING) & 1u) ? n * replay::kTagStride * sizeof(uint16_t) : 0;
+  L.F0 = o;    o += ((mask >> POL_FGD) & 1u) ? n * sizeof(double) : 0;
+  L.last = o;  o += general ? (n * sizeof(int) + 15) / 16 * 16 : 0;
+  L.total = o;
+  return L;
+}
+inline size_t wsum_lds(int N, unsigned mask, bool general) { return wsum_layout(N, mask, general).total; }
+inline bool wsum_fits(int N, unsigned mask, bool general) {
+  return N >= 1 && N <= kMaxNodes && wsum_lds(N, mask, general) <= kLdsMax;
+}
+}  // namespace wsum
+
 // ---- which instantiation a launch takes ----
 // The engine maps a form's code() to a function pointer in one switch over the enumerators below (no default: a form
 // without an instantiation does not compile clean); tests/native_host/plan_check.cpp enumerates every input.
@@ -696,6 +732,7 @@ struct RunReplica {
   int n_events = 0;
   bool has_delete = false;
   int dpcfg = 0;  // DotProduct: dimExtMethod | normMethod << 4
+  unsigned wmask = 0u;  // POL_WEIGHTED: the plugins with a positive weight (wsum::plugin_mask)
 };
 struct RunPlanInput {
   std::vector<RunReplica> reps;
@@ -715,7 +752,7 @@ struct RunPlanInput {
 constexpr int kPolRandomGo = 64;  // the k_random_go replicas
 constexpr int kPolFgdH = 66;      // the one-workgroup FGD replicas on k_hmemo beside wide ones on k_memo (split_fgd)
 
-enum GroupKernel { kRunRandomGo, kRunScan1, kRunMemo, kRunHmemo, kRunReplay, kRunNone };
+enum GroupKernel { kRunRandomGo, kRunScan1, kRunMemo, kRunHmemo, kRunReplay, kRunNone, kRunWsum };
 
 struct PlanGroup {
   int kind = 0;              // a policy, kPolFgdH, scan1::kPolMix or kPolRandomGo
@@ -724,6 +761,7 @@ struct PlanGroup {
   int side = -1;             // its side stream's index; -1: the engine stream
   int K = 1, S = 0;          // k_replay and k_scan1 groups: workgroups per replica, nodes per slice, dynamic LDS bytes
   size_t lds = 0;            // (k_replay: a co-resident grid the device cannot hold is narrowed at launch)
+  unsigned wmask = 0u;       // a k_wsum group: the union of its replicas' plugin masks (the launch's LDS layout)
 };
 
 struct RunPlan {
@@ -818,6 +856,12 @@ inline void plan_order(const RunPlanInput& in, RunPlan& pl) {
       if (in.reps[r].policy == pol && !in.reps[r].go_random) { pl.order.push_back(r); ++c; }
     add(pol, c);
   }
+  {  // the weighted combinations (k_wsum), after the policies' groups and before Go's Random
+    int c = 0;
+    for (int r = 0; r < R; ++r)
+      if (in.reps[r].policy == POL_WEIGHTED) { pl.order.push_back(r); ++c; }
+    add(POL_WEIGHTED, c);
+  }
   int c = 0;
   for (int r = 0; r < R; ++r)
     if (in.reps[r].go_random) { pl.order.push_back(r); ++c; }
@@ -830,10 +874,19 @@ inline void plan_order(const RunPlanInput& in, RunPlan& pl) {
 // a k_memo launch outside a split FGD run or the profile timers keep the launches back to back on the engine stream.
 inline void plan_kernels(const RunPlanInput& in, RunPlan& pl) {
   pl.concurrent = !in.timers && pl.groups.size() >= 2;
+  int first = 0;  // (make_run_plan sets g.first afterwards; plan_mix leaves a k_wsum group where it is)
   for (PlanGroup& g : pl.groups) {
+    const int g_first = first;
+    first += g.count;
     const bool fgd = g.kind == POL_FGD && in.run_mode != 2;
     if (g.kind == kPolRandomGo) {  // one workgroup per replica
       g.kernel = kRunRandomGo;
+    } else if (g.kind == POL_WEIGHTED) {  // k_wsum: one workgroup per replica over the whole cluster, no exchange
+      g.kernel = kRunWsum;
+      g.K = 1;
+      g.S = in.N;
+      for (int j = g_first; j < g_first + g.count; ++j) g.wmask |= in.reps[pl.order[j]].wmask;
+      g.lds = wsum::wsum_lds(in.N, g.wmask, pl.general);  // (the launcher refuses a cluster that does not fit)
     } else if (fgd && in.memo_ok) {  // (a split FGD run's wide group is launched first, behind its gate)
       g.kernel = kRunMemo;
       pl.concurrent = pl.concurrent && in.split_fgd;

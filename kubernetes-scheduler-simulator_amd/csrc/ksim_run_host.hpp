@@ -16,6 +16,7 @@ struct RunStats {
   int K = 0;         // workgroups per replica of the last replay launch that has a width (0: none had one)
   int memo = 0, hmemo = 0, rgo = 0, scan1 = 0;  // replicas replayed on k_memo / k_hmemo / k_random_go / k_scan1
   int launches = 0, streams = 0;                // replay launches, side streams they ran on (0: none)
+  int wsum = 0;      // replicas replayed on k_wsum (the weighted combinations)
   int ovl = 0;       // replicas the overlapped report took (k_report_overlap)
   int gate = 0;      // the residency gate: 0 none, 1 opened, -1 given up at its bound (stderr note)
   std::string kernels;     // the replay kernels launched, '+'-joined in launch order, each name once
@@ -41,6 +42,7 @@ inline int run_path(const RunStats& s, int R, int run_mode, bool sharded) {
   if (run_mode == 1 || s.step_path) return KSIM_PATH_STEP;
   if (s.rgo == R) return KSIM_PATH_RANDOM_GO;
   if (s.scan1 == R) return KSIM_PATH_SCAN1;
+  if (s.wsum == R && R > 0) return KSIM_PATH_WSUM;
   if (s.memo == 0 && s.hmemo == 0) return KSIM_PATH_REPLAY;
   if (s.memo == R) return KSIM_PATH_MEMO;
   if (s.hmemo == R) return KSIM_PATH_HMEMO;

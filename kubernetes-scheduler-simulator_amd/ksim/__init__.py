@@ -30,7 +30,8 @@ MAX_GPU = 8
 NUM_TAGS = 9
 
 POLICY = {"FGD": 0, "BestFit": 1, "DotProd": 2, "GpuPacking": 3, "GpuClustering": 4, "Random": 5,
-          "PWR": 6, "PWR+FGD": 7}
+          "PWR": 6, "PWR+FGD": 7, "Weighted": 8}
+NUM_PLUGINS = 7  # a "Weighted" weight vector: one weight per plugin id FGD .. PWR (0..6)
 GPUSEL = {"best": 0, "worst": 1, "random": 2, "FGD": 3, "PWR": 4, "DotProd": 5}
 # DotProduct's GpuPluginCfg (pkg/type/config.go:3-55)
 DIM_EXT = {"merge": 0, "share": 1, "divide": 2, "extend": 3}
@@ -41,13 +42,37 @@ DEFAULT_GPUSEL = {"FGD": "FGD", "BestFit": "best", "DotProd": "best", "GpuPackin
                   "GpuClustering": "best", "Random": "random", "PWR": "PWR", "PWR+FGD": "FGD"}
 
 
+# generate_config_and_run.py:243-245: the score plugins in the harness's order (the first wins a tie on the weight)
+PLUGIN_ORDER = ["Random", "DotProd", "GpuClustering", "GpuPacking", "BestFit", "FGD", "PWR"]
+
+
+def _is_int(s):
+    return s.isdigit()
+
+
 def parse_policy(name):
     """generate_run_scripts.py policy strings: "FGD", "PWR", "PWR 500 FGD 500", ... ->
-    (POLICY key, weights or None)."""
+    (POLICY key, weights or None).  The literal "PWR a FGD b" is ("PWR+FGD", (a, b)); any other string of
+    "Name weight" pairs ("FGD 700 BestFit 300"; the directory form "FGD_700_BestFit_300" too) is
+    ("Weighted", {name: weight})."""
     parts = name.replace("_", " ").split()  # the directory form "PWR_500_FGD_500" too (get_dir_name_from_method)
     if len(parts) == 4 and parts[0] == "PWR" and parts[2] == "FGD":
         return "PWR+FGD", (int(parts[1]), int(parts[3]))
+    if len(parts) >= 2 and len(parts) % 2 == 0 and all(p in PLUGIN_ORDER for p in parts[0::2]) and \
+            all(_is_int(p) for p in parts[1::2]) and len(set(parts[0::2])) == len(parts) // 2:
+        return "Weighted", {parts[i]: int(parts[i + 1]) for i in range(0, len(parts), 2)}
     return name, None
+
+
+def weighted_gpusel(weights, dim_ext=None):
+    """The default gpuSelMethod of a weighted combination (generate_config_and_run.py:264-277): the max-weight
+    plugin's own selector if that plugin is FGD, DotProd or PWR and dim_ext is not "merge", else "best"; the first
+    plugin in the harness's order wins a tie.  dim_ext None is this binding's default: merge for the DotProduct
+    term (Engine.set_policy), so a DotProd maximum then keeps "best", as the single DotProd policy does."""
+    top = max((n for n in PLUGIN_ORDER if weights.get(n, 0) > 0), key=lambda n: weights[n], default=None)
+    if dim_ext == "merge" or (top == "DotProd" and dim_ext is None):
+        return "best"
+    return top if top in ("FGD", "DotProd", "PWR") else "best"
 SCHEDULED, UNSCHEDULABLE, ERROR, DELETED = 0, 1, 2, 3
 
 
@@ -171,6 +196,7 @@ SIGNATURES = {
     "ksim_engine_set_policy": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_uint64]),
     "ksim_engine_set_power_model": (C.c_int, [_VP, C.c_int, _P(PowerModel)]),
     "ksim_engine_set_weights": (C.c_int, [_VP, C.c_int, C.c_int32, C.c_int32]),
+    "ksim_engine_set_plugin_weights": (C.c_int, [_VP, C.c_int, _P(C.c_int32)]),
     "ksim_engine_set_replica_wgs": (C.c_int, [_VP, C.c_int, C.c_int]),
     "ksim_trace_power_model": (C.c_int, [_VP, _P(PowerModel)]),
     "ksim_engine_filter_score": (C.c_int, [_VP, C.c_int, _P(Pod), C.c_int32, _P(C.c_uint8), _P(C.c_int32),
@@ -519,15 +545,29 @@ class Engine:
     def set_typical(self, r, tp, n):
         check(lib().ksim_engine_set_typical(self.h, r, tp, n), "set_typical")
 
-    def set_policy(self, r, policy="FGD", gpusel=None, seed=0, dim_ext=None, norm=None):
+    def set_policy(self, r, policy="FGD", gpusel=None, seed=0, dim_ext=None, norm=None, weights=None):
         """policy: a POLICY key or a generate_run_scripts.py string such as "PWR 500 FGD 500".
+        Any other string of "Name weight" pairs ("FGD 700 BestFit 300"), or policy="Weighted" with
+        weights={"PWR": 500, "FGD": 500}, is a weighted combination on k_wsum (ksim_engine_set_plugin_weights);
+        its default selector is weighted_gpusel's.
         DotProd: dim_ext / norm as generate_config_and_run.py's -dimext / -norm.  The default here is
         merge / max, the paper sweep's configuration (expected_run_scripts_0511.sh passes -dimext merge);
         NOTE the reference CLI's own default is -dimext share (generate_config_and_run.py:80), which also
         switches gpuSelMethod to DotProductScore -- pass dim_ext="share" to get that.  Like that script, a
         dim_ext other than merge selects GPUs with the DotProduct selector ("DotProd") unless gpusel says
         otherwise."""
-        policy, weights = parse_policy(policy)
+        policy, parsed = parse_policy(policy)
+        if policy == "Weighted":
+            weights = weights if weights is not None else parsed
+            if not weights:
+                raise ValueError("policy \"Weighted\" needs weights")
+            gs = gpusel or weighted_gpusel(weights, dim_ext)
+            check(lib().ksim_engine_set_policy(self.h, r, POLICY[policy], GPUSEL[gs], seed), "set_policy")
+            self.set_plugin_weights(r, weights)
+            if weights.get("DotProd", 0) > 0 or dim_ext is not None or norm is not None:
+                self.set_plugin_cfg(r, dim_ext or "merge", norm or "max")
+            return
+        weights = parsed
         if policy == "DotProd" and dim_ext not in (None, "merge") and gpusel is None:
             gpusel = "DotProd"  # generate_config_and_run.py:271-275
         gs = gpusel or DEFAULT_GPUSEL[policy]
@@ -547,6 +587,16 @@ class Engine:
 
     def set_weights(self, r, w_pwr, w_fgd):
         check(lib().ksim_engine_set_weights(self.h, r, w_pwr, w_fgd), "set_weights")
+
+    def set_plugin_weights(self, r, weights):
+        """weights: {plugin name: weight} over POLICY's plugins FGD .. PWR, e.g. {"FGD": 700, "BestFit": 300}
+        (a replica whose policy is "Weighted")."""
+        w = (C.c_int32 * NUM_PLUGINS)()
+        for name, v in weights.items():
+            if name not in POLICY or POLICY[name] >= NUM_PLUGINS:
+                raise KeyError("no score plugin %r" % (name,))
+            w[POLICY[name]] = int(v)
+        check(lib().ksim_engine_set_plugin_weights(self.h, r, w), "set_plugin_weights")
 
     def set_power_model(self, r, pm):
         check(lib().ksim_engine_set_power_model(self.h, r, C.byref(pm)), "set_power_model")
@@ -726,7 +776,8 @@ class Engine:
         others)."""
         k = C.c_int(0)
         check(lib().ksim_engine_last_run_path(self.h, C.byref(k)), "last_run_path")
-        return ["k_replay", "k_memo", "memo+k_replay", "k_step", "sharded", "k_hmemo", "k_random_go", "k_scan1"][k.value]
+        return ["k_replay", "k_memo", "memo+k_replay", "k_step", "sharded", "k_hmemo", "k_random_go", "k_scan1",
+                "k_pmemo", "k_wsum"][k.value]  # (8: the archived k_pmemo trial's number, never reported)
 
     def last_run_launches(self):
         """(replay launches, side streams they ran on concurrently; 0 = back to back) of the last run()."""
